@@ -36,6 +36,17 @@ void klt_amd_pyr_desc(KLT_TrackingContext tc, int ncols, int nrows, int nlevels,
 void klt_amd_track_desc(KLT_TrackingContext tc, klt_hip_track_desc *desc);
 /* KLT_HIP_EXACT (default) or KLT_HIP_FAST; env KLT_AMD_REDUCTION=fast sets FAST */
 void klt_amd_set_reduction(KLT_TrackingContext tc, int reduction);
+/* Forward-backward consistency check (klt_hip_set_fb in klt_hip.h has the
+   exact definition), off by default: with it on, KLTTrackFeatures and
+   KLTTrackSequence (which stays on its batched path) track every feature back
+   from img2 to img1 in the same kernel launch and reject it -- x = y = -1,
+   val = KLT_AMD_FB_REJECTED -- when it is lost on the way or returns farther
+   than max_dist pixels from where it started.  max_dist must be finite and
+   >= 0: otherwise -1 with a KLTWarning and the setting unchanged; 0 on
+   success.  KLTTrackFeatures with the check on and affineConsistencyCheck >= 0
+   or KLT_HIP_FAST sums is a KLTError. */
+#define KLT_AMD_FB_REJECTED -6
+int klt_amd_set_fb_check(KLT_TrackingContext tc, int on, float max_dist);
 
 /* The reference harness loop (example3.c:54-74 without REPLACE) in one call:
      for (i = 1; i < nframes; i++) {

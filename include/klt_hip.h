@@ -145,6 +145,35 @@ int klt_hip_set_track_impl(klt_hip_ctx *ctx, int impl);
    verdict loses frame j's feature.  0: a residue pass of its own.  Results do
    not depend on it. */
 int klt_hip_set_track_merge(klt_hip_ctx *ctx, int on);
+/* Forward-backward (FB) consistency check, off by default.  With it on, every
+   tracked frame img1 -> img2 of klt_hip_track (host or device arrays),
+   klt_hip_track_sequence, klt_hip_track_frames and klt_hip_track_frames_host
+   is followed, in the same tracker launch, by the reference's own step with
+   the two images exchanged -- KLTTrackFeatures(img2, img1) on a copy of the
+   forward result, same parameters, every level started from the forward
+   position, the residue taken against img2 -- for every feature the forward
+   step tracked.  The feature is rejected (x = y = -1, val =
+   KLT_HIP_FB_REJECTED) when the backward step loses it, or when it returns to
+   (xb, yb) with e = (xb - x0)^2 + (yb - y0)^2 > max_dist * max_dist, (x0, y0)
+   being where the frame started: five float operations each rounded to float,
+   the threshold one float product on the host.  A kept feature is exactly
+   the forward result; a rejected one is lost from that frame on.  max_dist
+   (pixels) must be finite and >= 0 (else -1, settings unchanged).
+   The FB kernels take the residue pass in place, so klt_hip_set_track_merge
+   is ignored while FB is on; the other tuning hooks apply and do not change
+   results.  Not covered, failing with -1 and a message before any launch:
+   KLT_HIP_FAST sums, klt_hip_track_frames_band (and the sharded drivers built
+   on it), klt_hip_track_affine.  klt_hip_ctx_reset turns FB off. */
+#define KLT_HIP_FB_REJECTED (-6)
+int klt_hip_set_fb(klt_hip_ctx *ctx, int on, float max_dist);
+int klt_hip_get_fb(klt_hip_ctx *ctx, int *on, float *max_dist);
+/* optional device table of e with FB on: row f (stride elements apart, stride
+   >= n) of a klt_hip_track_frames / _host call receives tracked frame f's e
+   per feature, row 0 that of a klt_hip_track call or klt_hip_track_sequence
+   step; -1.0f where there is no distance (the feature was lost before or by
+   the forward step, or by the backward one).  NULL clears it, and so does
+   klt_hip_ctx_reset.  The caller keeps the memory valid while it is set. */
+int klt_hip_set_fb_table(klt_hip_ctx *ctx, float *dev_err, long stride);
 /* tuning hook: 1 (default) raises the tracker waves' issue priority
    (s_setprio 3) so that, when the next chunk's pyramids are built beside the
    tracker (overlapped schedule, band calls with build-ahead), a feature's

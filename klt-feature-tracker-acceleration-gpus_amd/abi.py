@@ -11,6 +11,8 @@ import ctypes as C
 
 KLT_TRACKED, KLT_NOT_FOUND, KLT_SMALL_DET = 0, -1, -2
 KLT_MAX_ITERATIONS, KLT_OOB, KLT_LARGE_RESIDUE = -3, -4, -5
+# libklt_amd.so only (include/klt_amd.h): rejected by the forward-backward check
+KLT_AMD_FB_REJECTED = -6
 
 
 class FloatImageRec(C.Structure):

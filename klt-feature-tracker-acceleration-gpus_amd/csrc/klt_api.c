@@ -19,6 +19,7 @@
  *
  * There is no CPU fallback: a missing or failing GPU is a KLTError.
  */
+#include <float.h>
 #include <math.h>
 #include <pthread.h>
 #include <stdio.h>
@@ -48,6 +49,8 @@ typedef struct {
   int last_slot; /* slot holding the sequential-mode pyramid, -1 none */
   int last_w, last_h;
   int reduction; /* KLT_HIP_EXACT unless KLT_AMD_REDUCTION=fast */
+  int fb_on;     /* forward-backward check (klt_amd_set_fb_check), applied to the device context per call */
+  float fb_dist;
   /* affine consistency check: the feature list whose stored windows the
      device store holds, and per slot the aff_img whose data it holds */
   KLT_FeatureList aff_list;
@@ -141,6 +144,20 @@ int klt_amd_release_cached_devices(void)
 static void dev_check(KLT_TrackingContext tc, int rc, const char *what)
 {
   if (rc != 0) KLTError("(KLT) %s failed: %s", what, klt_hip_last_error(FULL(tc)->dev));
+}
+
+/* the forward-backward check of this tracking context onto its device context,
+   before every tracking call (the device context may be a parked one, or have
+   been set otherwise through klt_amd_device_context) */
+static void apply_fb(KLT_TrackingContext tc, const char *who)
+{
+  klt_ctx_full *f = FULL(tc);
+  if (f->fb_on && tc->affineConsistencyCheck >= 0)
+    KLTError("(%s) the forward-backward check does not combine with affineConsistencyCheck=%d", who,
+             tc->affineConsistencyCheck);
+  if (f->fb_on && f->reduction != KLT_HIP_EXACT)
+    KLTError("(%s) the forward-backward check needs exact sums (KLT_HIP_EXACT)", who);
+  dev_check(tc, klt_hip_set_fb(device_of(tc), f->fb_on, f->fb_dist), "forward-backward setting");
 }
 
 /* ------------------------------------------------------------------ */
@@ -832,6 +849,7 @@ EXPORT void KLTTrackFeatures(KLT_TrackingContext tc, KLT_PixelType *img1, KLT_Pi
              "the reference's stored window, trackFeatures.c:680-689)",
              tc->affine_window_width, tc->affine_window_height);
   dev = device_of(tc);
+  apply_fb(tc, "KLTTrackFeatures");
 
   if (tc->sequentialMode && tc->pyramid_last != NULL && f->last_slot >= 0) {
     if (f->last_w != ncols || f->last_h != nrows)
@@ -971,6 +989,7 @@ EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int
   if (ft && ft->nFeatures != n)
     KLTError("(KLTStoreFeatures) FeatureList and FeatureTable must have the same number of features");
   dev = device_of(tc);
+  apply_fb(tc, "KLTTrackSequence");
   seq_start = tc->sequentialMode && tc->pyramid_last != NULL && f->last_slot >= 0;
   if (seq_start && (f->last_w != ncols || f->last_h != nrows))
     KLTError("(KLTTrackSequence) Size of incoming image (%d by %d) is different from size of "
@@ -1100,4 +1119,15 @@ EXPORT void klt_amd_track_desc(KLT_TrackingContext tc, klt_hip_track_desc *td)
 EXPORT void klt_amd_set_reduction(KLT_TrackingContext tc, int reduction)
 {
   FULL(tc)->reduction = reduction;
+}
+
+EXPORT int klt_amd_set_fb_check(KLT_TrackingContext tc, int on, float max_dist)
+{
+  if (!(max_dist >= 0.0f) || max_dist > FLT_MAX) { /* NaN, negative, infinite */
+    KLTWarning("(klt_amd_set_fb_check) max_dist %g must be finite and >= 0", (double)max_dist);
+    return -1;
+  }
+  FULL(tc)->fb_on = on ? 1 : 0;
+  FULL(tc)->fb_dist = max_dist;
+  return 0;
 }

@@ -4,6 +4,9 @@
 //   pyramid.hip   k_pyr_l0 / k_pyr_l1 (fused default-parameter pyramid),
 //                 the generic one-pass kernels, k_min_eigen, k_synth
 //   track.hip     k_track_frames (the Newton loop), k_band_order
+//   track7.hip    k_track7 (the Newton loop of the default configuration)
+//                 both with forward-backward instances (k_*_fb); the kernels'
+//                 bodies are track_body.h / track7_body.h
 //   affine.hip    k_affine (the affine consistency check)
 //   runtime.hip   host side: device contexts, slots and banks, pipelines,
 //                 the klt_hip_* C ABI (include/klt_hip.h)
@@ -133,6 +136,14 @@ struct TrkFramesArgs {
   long tstride;  // table row stride (elements); tx == nullptr: no table
   unsigned long long *count;  // non-null: [kCountSlots] 2x2 systems formed, [kCountSlots] gather round trips
 };
+// forward-backward check (klt_hip_set_fb): the FB kernel instances take this
+// beside TrkFramesArgs, so the FB-off instances keep their argument layout
+struct TrkFbArgs {
+  float t2;     // max_dist * max_dist, rounded to float on the host
+  float *err;   // optional: row j receives frame j's squared return distance (-1: none); nullptr: no table
+  long stride;  // its row stride (elements)
+};
+constexpr int kFbRejected = KLT_HIP_FB_REJECTED;
 constexpr int kCountSlots = 64;  // counter pairs (the host sums them)
 constexpr int kProfN = 12;       // instrumented build: counters per wave
 
@@ -191,12 +202,14 @@ hipError_t launch_selftest_div(const float *a, const float *b, float *out, int n
 
 // the tracker: one wave per feature; patch/win7 select the lane-patch gather
 // and the compiled-in 7x7 window, npx the pixels-per-lane instance
+// fb != nullptr: the forward-backward instances (exact sums, no band checks)
 hipError_t launch_track_frames(hipStream_t st, bool exact, bool li, bool patch, bool win7, int npx,
-                               const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y, int *v, int n);
+                               const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y, int *v, int n,
+                               const TrkFbArgs *fb = nullptr);
 // track7.hip: the default configuration (7x7 window, exact sums, no gain/bias,
 // one wave per feature) with the latency-lean pass; band: escape checks
 hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y,
-                         int *v, int n, const char **name = nullptr);
+                         int *v, int n, const char **name = nullptr, const TrkFbArgs *fb = nullptr);
 // band-sorted processing order (one workgroup); count != nullptr: keep only
 // live features with own_lo <= y < own_hi and store how many
 hipError_t launch_band_order(hipStream_t st, const float *fy, const int *fv, int n, int nrows, int *perm,

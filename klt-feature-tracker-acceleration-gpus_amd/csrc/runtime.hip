@@ -308,6 +308,12 @@ struct klt_hip_ctx {
   size_t pl_cap[2][KLT_HIP_MAX_LEVELS] = {};
   int track_impl = 0;    // 0: track7.hip for the default configuration, 1: the generic k_track_frames_g
   const char *track_kernel = nullptr;  // instance name of the last tracker launch (klt_hip_track_kernel)
+  // forward-backward check (klt_hip_set_fb): off by default; the optional
+  // device table of squared return distances (klt_hip_set_fb_table)
+  int fb_on = 0;
+  float fb_dist = 0.0f;
+  float *fb_tab = nullptr;
+  long fb_stride = 0;
   // band calls: 1 = the next chunk's frames are ready when the call is made
   // (not written by work still queued on the tracking stream), so its
   // build-ahead waits for its bank and for this chunk's processing order
@@ -854,10 +860,24 @@ int order_features(klt_hip_ctx *c, hipStream_t st, int nrows, const float *y, co
   return 0;
 }
 
-// ordered: the caller ran order_features into b already
+// The forward-backward check (klt_hip_set_fb) has instances for exact sums on
+// whole-frame pyramids only: anything else fails before a launch.
+int fb_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const char *who) {
+  if (!c->fb_on) return 0;
+  if (band) return fail(c, "%s: the forward-backward check does not cover band calls (klt_hip_set_fb)", who);
+  if (d->reduction != KLT_HIP_EXACT)
+    return fail(c, "%s: the forward-backward check needs KLT_HIP_EXACT sums (klt_hip_set_fb)", who);
+  return 0;
+}
+
+// ordered: the caller ran order_features into b already; fb_row: the
+// forward-backward table row of this launch's first frame
 int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc *d, const TrkArgs &a,
                         const TrkFramesArgs &b, float *x, float *y, int *v, int n, const float *own = nullptr,
-                        bool ordered = false) {
+                        bool ordered = false, long fb_row = 0) {
+  if (fb_refused(c, d, own != nullptr || a.escape != nullptr, "track")) return -1;
+  if (c->fb_on && c->fb_tab && c->fb_stride < n)
+    return fail(c, "track: forward-backward table stride %ld < n %d", c->fb_stride, n);
   TimedScope ts(c, T_TRACK, st, b.nframes);
   const int npx = d->window_width * d->window_height;
   const bool exact = d->reduction == KLT_HIP_EXACT, li = d->lighting_insensitive != 0;
@@ -898,9 +918,18 @@ int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc
     }
   }
   HMARK_IN("track_args");
-  if (t7) return launched(c, "k_track7", launch_track7(st, aa.escape != nullptr, aa, b2, x, y, v, n, &c->track_kernel));
-  c->track_kernel = "kltdev::k_track_frames_g";
-  return launched(c, "k_track_frames", launch_track_frames(st, exact, li, patch, win7, npx, aa, b2, x, y, v, n));
+  TrkFbArgs fb{};
+  if (c->fb_on) {
+    const volatile float t2 = c->fb_dist * c->fb_dist;  // one float product
+    fb.t2 = t2;
+    fb.err = c->fb_tab ? c->fb_tab + fb_row * c->fb_stride : nullptr;
+    fb.stride = c->fb_stride;
+  }
+  const TrkFbArgs *fbp = c->fb_on ? &fb : nullptr;
+  if (t7)
+    return launched(c, "k_track7", launch_track7(st, aa.escape != nullptr, aa, b2, x, y, v, n, &c->track_kernel, fbp));
+  c->track_kernel = fbp ? "kltdev::k_track_frames_g_fb" : "kltdev::k_track_frames_g";
+  return launched(c, "k_track_frames", launch_track_frames(st, exact, li, patch, win7, npx, aa, b2, x, y, v, n, fbp));
 }
 
 // The three banks live in one device arena per context: for each bank, level
@@ -1401,6 +1430,10 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->track_merge = 1;
   c->track_prio = 1;
   c->track_impl = 0;
+  c->fb_on = 0;
+  c->fb_dist = 0.0f;
+  c->fb_tab = nullptr;
+  c->fb_stride = 0;
   c->serial_frames = 1;
   c->ahead_ready = 0;
   c->prof = nullptr;
@@ -1709,6 +1742,30 @@ KLT_API int klt_hip_set_track_impl(klt_hip_ctx *c, int impl) {
   return 0;
 }
 
+KLT_API int klt_hip_set_fb(klt_hip_ctx *c, int on, float max_dist) {
+  if (!c) return fail(c, "set_fb: null context");
+  if (!(max_dist >= 0.0f) || !isfinite(max_dist))
+    return fail(c, "set_fb: max_dist %g must be finite and >= 0", (double)max_dist);
+  c->fb_on = on ? 1 : 0;
+  c->fb_dist = max_dist;
+  return 0;
+}
+
+KLT_API int klt_hip_get_fb(klt_hip_ctx *c, int *on, float *max_dist) {
+  if (!c) return fail(c, "get_fb: null context");
+  if (on) *on = c->fb_on;
+  if (max_dist) *max_dist = c->fb_dist;
+  return 0;
+}
+
+KLT_API int klt_hip_set_fb_table(klt_hip_ctx *c, float *dev_err, long stride) {
+  if (!c) return fail(c, "set_fb_table: null context");
+  if (dev_err && stride < 1) return fail(c, "set_fb_table: stride %ld < 1", stride);
+  c->fb_tab = dev_err;
+  c->fb_stride = dev_err ? stride : 0;
+  return 0;
+}
+
 KLT_API int klt_hip_set_track_count(klt_hip_ctx *c, int on) {
   if (!c) return fail(c, "set_track_count: null context");
   if (use_device(c)) return -1;
@@ -1855,6 +1912,7 @@ KLT_API int klt_hip_track(klt_hip_ctx *c, int s1, int s2, const klt_hip_track_de
   for (int l = 0; l < A.nlev; ++l)
     if (A.lv[l].w != B.lv[l].w || A.lv[l].h != B.lv[l].h) return fail(c, "track: slot size mismatch");
   if (check_window(c, d)) return -1;
+  if (fb_refused(c, d, false, "track")) return -1;
   const int npx = d->window_width * d->window_height;
   if (n <= 0) return 0;
   if (use_device(c)) return -1;
@@ -1966,6 +2024,8 @@ KLT_API int klt_hip_track_affine(klt_hip_ctx *c, int s1, int s2, const klt_hip_t
   if (ad->window_width < 3 || ad->window_height < 3 || ad->window_width % 2 == 0 || ad->window_height % 2 == 0)
     return fail(c, "track_affine: affine window %dx%d must be odd and >= 3", ad->window_width,
                 ad->window_height);
+  if (c->fb_on)
+    return fail(c, "track_affine: the forward-backward check does not combine with the affine check (klt_hip_set_fb)");
   if (n <= 0) return 0;
   if (s1 < 0 || s1 >= KLT_HIP_MAX_SLOTS || s2 < 0 || s2 >= KLT_HIP_MAX_SLOTS)
     return fail(c, "track_affine: bad slot");
@@ -2193,7 +2253,7 @@ void band_planes(const BandSpec &b, int &p0, int &p1) {
 int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td,
                       const unsigned char *frames, long pitch, long stride, int nframes, int chunk, float *x,
                       float *y, int *val, int n, float *tab_x, float *tab_y, int *tab_val, long tab_stride,
-                      const BandSpec *band) {
+                      const BandSpec *band, long fb_row0 = 0) {
 #ifdef KLT_HOST_PROF
   HostMarks hm_;
 #endif
@@ -2208,6 +2268,9 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
   if (ntab && tab_stride < n) return fail(c, "track_frames: table stride %ld < n %d", tab_stride, n);
   if (pitch < pd->ncols) return fail(c, "track_frames: pitch %ld < ncols %d", pitch, pd->ncols);
   if (check_window(c, td)) return -1;
+  if (fb_refused(c, td, band != nullptr, band ? "track_frames_band" : "track_frames")) return -1;
+  if (c->fb_on && c->fb_tab && c->fb_stride < n)
+    return fail(c, "track_frames: forward-backward table stride %ld < n %d", c->fb_stride, n);
   {
     const TrkLevel p0 = prev_level(c, 0);
     int nl = c->prev.bank < 0 ? c->slot[c->prev.slot].nlev : c->bank[c->prev.bank].nlev;
@@ -2372,7 +2435,8 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
       if (!c->ev_go) HIPCHK(c, hipEventCreateWithFlags(&c->ev_go, hipEventDisableTiming));
       HIPCHK(c, hipEventRecord(c->ev_go, c->stream));
     }
-    if (n > 0 && track_frames_launch(c, c->stream, td, a, b, x, y, val, n, band ? band->own : nullptr, true))
+    if (n > 0 &&
+        track_frames_launch(c, c->stream, td, a, b, x, y, val, n, band ? band->own : nullptr, true, fb_row0 + j0))
       return -1;
     HMARK("track");
     if (!serial && !ahead && c->prev.bank >= 0) HIPCHK(c, hipEventRecord(c->ev_bfree[c->prev.bank], c->stream));
@@ -2485,6 +2549,7 @@ KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
                                       float *x, float *y, int *val, int n, klt_hip_rows_fn rows, void *user) {
   if (!c || !pd || !td || (nframes > 0 && !frames)) return fail(c, "track_frames_host: null argument");
   if (chunk < 1 || nframes < 0 || n < 0) return fail(c, "track_frames_host: bad nframes/chunk/n");
+  if (fb_refused(c, td, false, "track_frames_host")) return -1;
   if (n > 0 && (!x || !y || !val)) return fail(c, "track_frames_host: null feature arrays");
   for (int f = 0; f < nframes; ++f)
     if (!frames[f]) return fail(c, "track_frames_host: frame %d is NULL", f);
@@ -2573,7 +2638,7 @@ KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rows[k], 0));  // the rows slot's last D2H is done
     if (nt > 0 && track_frames_impl(c, pd, td, c->d_ring + (size_t)k * F * fb + skip * fb, pd->ncols, fb, nt, F,
                                     dx, dy, dv, n, rows ? rx : nullptr, rows ? ry : nullptr, rows ? rv : nullptr,
-                                    n, nullptr))
+                                    n, nullptr, t0))
       return -1;
     HIPCHK(c, hipEventRecord(c->ev_ring_free[k], c->stream));
     if (rows && n > 0 && nt > 0) {

@@ -748,101 +748,32 @@ __device__ __forceinline__ void track_feature_g(PROF_DECL const TrkArgs &a, cons
 }
 
 // BAND: band-built pyramids (klt_hip_track_frames_band) -- the escape checks
+// FB: the forward-backward instances (klt_hip_set_fb).  A feature tracked in
+// frame j is tracked again with the two pyramids exchanged, from its forward
+// position (KLTTrackFeatures(img2, img1) on a copy of the list), and rejected
+// (x = y = -1, val = kFbRejected) when that loses it or ends farther than
+// sqrt(fb.t2) from where frame j started; a kept feature is the forward
+// result.  The residue is not deferred (frame j's status comes first), and
+// every level call starts with an empty patch cache.
+// The body is track_body.h, shared by the two kernels below.
 template <int G, int PPL, bool PATCH, int WIN, bool EXACT, bool LI, bool BAND>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KLT_TRACK_WAVES))) void k_track_frames_g(TrkArgs a, TrkFramesArgs b, float *__restrict__ fx,
                                                            float *__restrict__ fy, int *__restrict__ fv, int n) {
   constexpr int LG = kWave / G;
   __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][6 * G * (LG * PPL + 4) + 16];
-  if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  // consecutive workgroups land on the 8 XCDs round-robin: give each XCD a
-  // contiguous run of the (band-sorted) order so its L2 sees one image band
-  if (b.n_dev) n = *b.n_dev;
-  // band mode: the grid is sized for every feature, but only the n_dev kept
-  // ones are processed -- spread THEIR blocks over the 8 XCDs (a per-XCD run
-  // sized for all features would put a small band on one XCD)
-  const int xcd_per = b.n_dev && b.xcd_per > 0 ? ((n + kBlock / kWave * G - 1) / (kBlock / kWave * G) + 7) / 8
-                                                 : b.xcd_per;
-  if (xcd_per > 0 && (int)(blockIdx.x / 8) >= xcd_per) return;  // past this XCD's run: no duplicate slots
-  const int blk = xcd_per > 0 ? (int)(blockIdx.x % 8) * xcd_per + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-  const int s0 = (blk * (kBlock / kWave) + wave) * G;
-  if (s0 >= n) return;  // whole wave; the kernel has no workgroup barrier
-  const int g = lane / LG, slot = s0 + g;
-  const bool exists = slot < n;
-  const int f = exists ? (b.perm ? b.perm[slot] : slot) : 0;
-  float x = 0.0f, y = 0.0f;
-  int v = -1;
-  if (exists) {
-    x = uni<G>(fx[f]);
-    y = uni<G>(fy[f]);
-    v = uni<G>(fv[f]);
-  }
-  const GroupWin<G, PPL, PATCH, WIN> w = group_window<G, PPL, PATCH, WIN>(a.ww, a.wh, lane);
-  {  // row pads of the ordered-sum staging stay +0 for the whole kernel
-    float *red = red_all[wave];
-    constexpr int RED = 6 * G * (LG * PPL + 4) + 16;
-    for (int i = lane; i < RED; i += kWave) red[i] = 0.0f;
-    lds_wave_sync();
-  }
-  const bool head = exists && (lane % LG) == 0;
-#ifdef KLT_TRACK_PROF
-  Prof prof;
-  const unsigned long long wall0 = wall_clock64();
-#endif
-  // deferred residues (ResCarry): one-feature waves, exact sums, default gain
-  // (band mode too: the residue's rows were checked against the band at frame
-  // j's final position, and an escape voids the whole chunk anyway)
-  const bool merge = G == 1 && EXACT && !LI && a.merge_res && a.nlev >= 2;
-  ResCarry<PPL> rc;
-  TrkCount cnt;
-  for (int j = 0; j < b.nframes; ++j) {
-    const bool job = rc.pending;  // frame j-1 is tentatively tracked at (x, y)
-    const bool live = exists && (v >= 0 || job);  // lost features are not tracked (:1346)
-    const float xp = x, yp = y;
-    int rstat = kTracked;
-    PROF_T(t_f0);
-    if (wave_any(live)) {
-      auto LA = [&](int r) { return j == 0 ? a.A[r] : at_frame(a.B[r], (long)(j - 1) * b.lfs[r]); };
-      track_feature_g<G, PPL, PATCH, WIN, EXACT, LI, BAND>(
-          PROF_ARG a, w, LA, [&](int r) { return at_frame(a.B[r], (long)j * b.lfs[r]); }, x, y, v, live, lane,
-          red_all[wave], rc, job, merge && j + 1 < b.nframes, LA(0), rstat, cnt);
-    }
-    PROF_ADD(4, t_f0);
-    if (job) {  // frame j-1's verdict came with frame j's first pass
-      if (rstat != kTracked) {
-        x = -1.0f;
-        y = -1.0f;
-        v = rstat;
-      }
-      if (b.tx && head) {
-        b.tx[(j - 1) * b.tstride + f] = rstat != kTracked ? -1.0f : xp;
-        b.ty[(j - 1) * b.tstride + f] = rstat != kTracked ? -1.0f : yp;
-        b.tv[(j - 1) * b.tstride + f] = rstat;
-      }
-    }
-    if (b.tx && head && !rc.pending) {
-      b.tx[j * b.tstride + f] = x;
-      b.ty[j * b.tstride + f] = y;
-      b.tv[j * b.tstride + f] = v;
-    }
-  }
-  if (head) {
-    fx[f] = x;
-    fy[f] = y;
-    fv[f] = v;
-    if (b.count) {  // one pair of atomics per feature per launch, spread over kCountSlots addresses
-      const int k = (blk * (kBlock / kWave) + wave) & (kCountSlots - 1);
-      atomicAdd(&b.count[k], (unsigned long long)cnt.solves);
-      atomicAdd(&b.count[kCountSlots + k], (unsigned long long)cnt.passes);
-    }
-  }
-#ifdef KLT_TRACK_PROF
-  prof.c[8] = wall0;
-  prof.c[9] = wall_clock64();
-  prof.c[7] = prof.c[9] - wall0;  // constant-rate ticks over the wave's life
-  if (b.prof && lane == 0)
-    for (int k = 0; k < kProfN; ++k) b.prof[(long)(blk * (kBlock / kWave) + wave) * kProfN + k] = prof.c[k];
-#endif
+  constexpr bool FB = false;
+  const TrkFbArgs fb{};
+#include "track_body.h"
+}
+
+template <int G, int PPL, bool PATCH, int WIN, bool LI>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KLT_TRACK_WAVES))) void k_track_frames_g_fb(
+    TrkArgs a, TrkFramesArgs b, TrkFbArgs fb, float *__restrict__ fx, float *__restrict__ fy, int *__restrict__ fv,
+    int n) {
+  constexpr int LG = kWave / G;
+  __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][6 * G * (LG * PPL + 4) + 16];
+  constexpr bool EXACT = true, BAND = false, FB = true;
+#include "track_body.h"
 }
 
 // ---------------------------------------------------------------------------
@@ -975,10 +906,39 @@ void launch_sel(bool patch, bool win7, int npx, hipStream_t st, const TrkArgs &a
   else launch_g<1, 16, false, 0, EXACT, LI>(st, a, b, x, y, v, n);
 }
 
+template <int G, int PPL, bool PATCH, int WIN, bool LI>
+void launch_g_fb(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkFbArgs &fb, float *x, float *y,
+                 int *v, int n) {
+  const int per = (kBlock / kWave) * G;
+  const int nb = (n + per - 1) / per;
+  const int grid = b.xcd_per > 0 ? 8 * b.xcd_per : nb;
+  hipLaunchKernelGGL((k_track_frames_g_fb<G, PPL, PATCH, WIN, LI>), dim3(grid), dim3(kBlock), 0, st, a, b, fb, x, y, v,
+                     n);
+}
+
+// launch_sel's choice of instance, for the forward-backward kernels
+template <bool LI>
+void launch_sel_fb(bool patch, bool win7, int npx, hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b,
+                   const TrkFbArgs &fb, float *x, float *y, int *v, int n) {
+  if (patch && win7) launch_g_fb<1, 1, true, 7, LI>(st, a, b, fb, x, y, v, n);
+  else if (patch) launch_g_fb<1, 1, true, 0, LI>(st, a, b, fb, x, y, v, n);
+  else if (win7) launch_g_fb<1, 1, false, 7, LI>(st, a, b, fb, x, y, v, n);
+  else if (npx <= kWave) launch_g_fb<1, 1, false, 0, LI>(st, a, b, fb, x, y, v, n);
+  else if (npx <= 4 * kWave) launch_g_fb<1, 4, false, 0, LI>(st, a, b, fb, x, y, v, n);
+  else launch_g_fb<1, 16, false, 0, LI>(st, a, b, fb, x, y, v, n);
+}
+
 }  // namespace
 
 hipError_t launch_track_frames(hipStream_t st, bool exact, bool li, bool patch, bool win7, int npx,
-                               const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y, int *v, int n) {
+                               const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y, int *v, int n,
+                               const TrkFbArgs *fb) {
+  if (fb) {  // the runtime refuses band calls and fast sums with the check on
+    if (!exact || a.escape) return hipErrorInvalidValue;
+    if (li) launch_sel_fb<true>(patch, win7, npx, st, a, b, *fb, x, y, v, n);
+    else launch_sel_fb<false>(patch, win7, npx, st, a, b, *fb, x, y, v, n);
+    return hipGetLastError();
+  }
   if (exact) {
     if (li) launch_sel<true, true>(patch, win7, npx, st, a, b, x, y, v, n);
     else launch_sel<true, false>(patch, win7, npx, st, a, b, x, y, v, n);

@@ -516,128 +516,36 @@ __device__ int level7(const TrkArgs &a, const Lev &A, const Lev &B, float x1, fl
 // NL > 0: the pyramid depth as a compile-time constant (the default 2), so
 // the level loops unroll and every level's fields are loop-invariant scalars;
 // NL == 0 reads a.nlev
+//
+// The body is track7_body.h, shared with k_track7_fb below.
+// FB: the forward-backward instance (klt_hip_set_fb).  After frame j's forward
+// track (image 1 = lev_prev(j), image 2 = bank frame j) a tracked feature goes
+// through the same level loop with the two images exchanged, from its forward
+// position -- KLTTrackFeatures(img2, img1) on a copy of the list -- and is
+// rejected (x = y = -1, val = kFbRejected) when that loses it or ends farther
+// than sqrt(fb.t2) from where frame j started.  A kept feature is the forward
+// result.  Frame j's final status must be known before the backward pass, so
+// the residue is not deferred (a.merge_res is ignored).  Each level7 call
+// starts with an empty corner-reuse cache (LevState::bpx), so no corners of
+// one direction's image 2 reach the other's or the next frame's; the bounds
+// thresholds (oobx/ooby) depend on the level's size only and serve both.
 template <bool BAND, bool AOS, int NL, bool FAST = false>
 __global__ __launch_bounds__(kBlock) void k_track7(TrkArgs a, TrkFramesArgs b, float *__restrict__ fx,
                                                    float *__restrict__ fy, int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRows * kRow + 4];
-  if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  if (b.n_dev) n = *b.n_dev;
-  // XCD-major block order over the (band-sorted) features actually processed
-  const int xcd_per = b.n_dev && b.xcd_per > 0 ? ((n + kWaves - 1) / kWaves + 7) / 8 : b.xcd_per;
-  if (xcd_per > 0 && (int)(blockIdx.x / 8) >= xcd_per) return;
-  const int blk = xcd_per > 0 ? (int)(blockIdx.x % 8) * xcd_per + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-  const int slot = blk * kWaves + wave;
-  if (slot >= n) return;  // whole wave; no workgroup barrier in this kernel
-  const int f = u(b.perm ? b.perm[slot] : slot);
-  float *red = red_all[wave];
-  for (int i = lane; i < kRows * kRow + 4; i += kWave) red[i] = 0.0f;  // pads stay +0
-  wave_lds_sync();
-  // lane p < 49: window pixel p; lanes past the window take the last pixel's
-  // offsets (valid addresses) and contribute nothing
-  const bool on = lane < kNpx;
-  const int pl = on ? lane : kNpx - 1;
-  const float fi = (float)(pl % kWin - kHw), fj = (float)(pl / kWin - kHw);  // x + i in the reference: int i as float
+  constexpr bool FB = false;
+  const TrkFbArgs fb{};
+#include "track7_body.h"
+}
 
-  float x = u(fx[f]), y = u(fy[f]);
-  int v = u(fv[f]);
-  const int nlev = NL > 0 ? NL : a.nlev;
-  const bool merge = a.merge_res && nlev >= 2;
-  Pending pd;
-  Counts cnt;
-#ifdef KLT_TRACK_PROF
-  const unsigned long long wall0 = wall_clock64();
-#endif
-  for (int j = 0; j < b.nframes; ++j) {
-    T7_T(t_f0);
-    const bool job = pd.on;  // frame j-1 is tentatively tracked at (x, y)
-    const float xp = x, yp = y;
-    int rstat = kTracked;
-    if (v >= 0 || job) {
-      // one frame of KLTTrackFeatures for this feature (:1348-1437)
-      const Lev R = lev_prev(a, b, 0, j);
-      float xl = x, yl = y;
-#pragma unroll
-      for (int r = nlev - 1; r >= 0; --r) {  // xloc /= subsampling, nlev times (:1352-1355)
-        xl = u(a.ss_inv != 0.0f ? xl * a.ss_inv : xl / a.ss);
-        yl = u(a.ss_inv != 0.0f ? yl * a.ss_inv : yl / a.ss);
-      }
-      float xo = xl, yo = yl;
-      int val = kTracked;
-      bool lost_prev = false;
-#pragma unroll
-      for (int r = nlev - 1; r >= 0; --r) {
-        xl = u(xl * a.ss);
-        yl = u(yl * a.ss);
-        xo = u(xo * a.ss);
-        yo = u(yo * a.ss);
-        const Lev LA = lev_prev(a, b, r, j);
-        const Lev LB = lev_of(a.B[r], (long)j * b.lfs[r], a.oobx[r], a.ooby[r]);
-        const bool lj = job && r == nlev - 1;
-        T7_T(t_l0);
-        val = level7<BAND, AOS, FAST>(a, LA, LB, xl, yl, xo, yo, lane, fi, fj, on, red, r == 0,
-                           merge && r == 0 && j + 1 < b.nframes, pd, lj, R, rstat, lost_prev, cnt);
-        T7_ADD(10, t_l0);
-        if (lost_prev) break;
-        if (val == kSmallDet || val == kOOB) break;
-      }
-      if (!lost_prev) {
-        const bool border = xo < a.borderx || xo > a.ncols - 1 - a.borderx || yo < a.bordery ||
-                            yo > a.nrows - 1 - a.bordery;
-        if (val == kOOB || border) {
-          pd.on = false;  // outside the border: OOB whatever the residue (trackFeatures.c:1383-1398)
-          x = -1.0f;
-          y = -1.0f;
-          v = kOOB;
-        } else if (val != kTracked) {
-          x = -1.0f;
-          y = -1.0f;
-          v = val;
-        } else {
-          x = xo;
-          y = yo;
-          v = kTracked;
-        }
-      }
-    }
-    if (job) {  // frame j-1's verdict came with frame j's first pass
-      if (rstat != kTracked) {
-        x = -1.0f;
-        y = -1.0f;
-        v = rstat;
-      }
-      if (b.tx && lane == 0) {
-        b.tx[(j - 1) * b.tstride + f] = rstat != kTracked ? -1.0f : xp;
-        b.ty[(j - 1) * b.tstride + f] = rstat != kTracked ? -1.0f : yp;
-        b.tv[(j - 1) * b.tstride + f] = rstat;
-      }
-    }
-    if (b.tx && lane == 0 && !pd.on) {
-      b.tx[j * b.tstride + f] = x;
-      b.ty[j * b.tstride + f] = y;
-      b.tv[j * b.tstride + f] = v;
-    }
-    T7_ADD(4, t_f0);
-  }
-#ifdef KLT_TRACK_PROF
-  cnt.c[5] = cnt.solves;
-  cnt.c[6] = cnt.passes;
-  cnt.c[8] = wall0;
-  cnt.c[9] = wall_clock64();
-  cnt.c[7] = cnt.c[9] - wall0;
-  if (b.prof && lane == 0)
-    for (int k = 0; k < kProfN; ++k) b.prof[(long)slot * kProfN + k] = cnt.c[k];
-#endif
-  if (lane == 0) {
-    fx[f] = x;
-    fy[f] = y;
-    fv[f] = v;
-    if (b.count) {
-      const int k = slot & (kCountSlots - 1);
-      atomicAdd(&b.count[k], (unsigned long long)cnt.solves);
-      atomicAdd(&b.count[kCountSlots + k], (unsigned long long)cnt.passes);
-    }
-  }
+// the forward-backward instances: whole-frame pyramids, exact sums
+template <bool AOS, int NL>
+__global__ __launch_bounds__(kBlock) void k_track7_fb(TrkArgs a, TrkFramesArgs b, TrkFbArgs fb,
+                                                      float *__restrict__ fx, float *__restrict__ fy,
+                                                      int *__restrict__ fv, int n) {
+  __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRows * kRow + 4];
+  constexpr bool BAND = false, FAST = false, FB = true;
+#include "track7_body.h"
 }
 
 }  // namespace
@@ -668,7 +576,7 @@ static int oob_threshold(int n) {
 }
 
 hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const TrkFramesArgs &b, float *x, float *y,
-                         int *v, int n, const char **name) {
+                         int *v, int n, const char **name, const TrkFbArgs *fb) {
   TrkArgs a = a_in;
   for (int l = 0; l < KLT_HIP_MAX_LEVELS; ++l) {
     a.oobx[l] = oob_threshold(a.B[l].w);
@@ -679,6 +587,20 @@ hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const T
   // band: escape checks (klt_hip_track_frames_band); aos: interleaved levels
   // (interleaved levels are the fused path's, always two levels deep)
   const bool two = KLT_T7_NL2 && a.nlev == 2;
+  if (fb) {  // the runtime refuses band calls and fast sums with the check on
+    if (band || a.fast) return hipErrorInvalidValue;
+    if (name)
+      *name = a.aos && two ? "kltdev::k_track7_fb<true, 2>"
+              : a.aos      ? "kltdev::k_track7_fb<true, 0>"
+                           : "kltdev::k_track7_fb<false, 0>";
+    if (a.aos && two)
+      hipLaunchKernelGGL((k_track7_fb<true, 2>), dim3(grid), dim3(kBlock), 0, st, a, b, *fb, x, y, v, n);
+    else if (a.aos)
+      hipLaunchKernelGGL((k_track7_fb<true, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, *fb, x, y, v, n);
+    else
+      hipLaunchKernelGGL((k_track7_fb<false, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, *fb, x, y, v, n);
+    return hipGetLastError();
+  }
   // the instance's name as rocprofv3 reports it (bench.py matches PMC summaries on it)
   if (name)
     *name = a.fast ? (band ? "kltdev::k_track7<true, true, 2, true>" : "kltdev::k_track7<false, true, 2, true>")

@@ -1,0 +1,167 @@
+// track7_body.h -- the body shared by k_track7 and k_track7_fb (track7.hip),
+// included inside each kernel: the FB-off kernels keep their by-value
+// arguments and compile to what they were before the forward-backward
+// instances existed.  The including kernel provides: the template parameters
+// BAND, AOS, NL, FAST; constexpr bool FB; TrkArgs a; TrkFramesArgs b;
+// TrkFbArgs fb; fx, fy, fv, n; and the LDS array red_all.
+  if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  if (b.n_dev) n = *b.n_dev;
+  // XCD-major block order over the (band-sorted) features actually processed
+  const int xcd_per = b.n_dev && b.xcd_per > 0 ? ((n + kWaves - 1) / kWaves + 7) / 8 : b.xcd_per;
+  if (xcd_per > 0 && (int)(blockIdx.x / 8) >= xcd_per) return;
+  const int blk = xcd_per > 0 ? (int)(blockIdx.x % 8) * xcd_per + (int)(blockIdx.x / 8) : (int)blockIdx.x;
+  const int slot = blk * kWaves + wave;
+  if (slot >= n) return;  // whole wave; no workgroup barrier in this kernel
+  const int f = u(b.perm ? b.perm[slot] : slot);
+  float *red = red_all[wave];
+  for (int i = lane; i < kRows * kRow + 4; i += kWave) red[i] = 0.0f;  // pads stay +0
+  wave_lds_sync();
+  // lane p < 49: window pixel p; lanes past the window take the last pixel's
+  // offsets (valid addresses) and contribute nothing
+  const bool on = lane < kNpx;
+  const int pl = on ? lane : kNpx - 1;
+  const float fi = (float)(pl % kWin - kHw), fj = (float)(pl / kWin - kHw);  // x + i in the reference: int i as float
+
+  float x = u(fx[f]), y = u(fy[f]);
+  int v = u(fv[f]);
+  const int nlev = NL > 0 ? NL : a.nlev;
+  const bool merge = !FB && a.merge_res && nlev >= 2;
+  Pending pd;
+  Counts cnt;
+#ifdef KLT_TRACK_PROF
+  const unsigned long long wall0 = wall_clock64();
+#endif
+  for (int j = 0; j < b.nframes; ++j) {
+    T7_T(t_f0);
+    const bool job = pd.on;  // frame j-1 is tentatively tracked at (x, y)
+    const float xp = x, yp = y;
+    int rstat = kTracked;
+    if (v >= 0 || job) {
+      // one frame of KLTTrackFeatures for this feature (:1348-1437)
+      const Lev R = lev_prev(a, b, 0, j);
+      float xl = x, yl = y;
+#pragma unroll
+      for (int r = nlev - 1; r >= 0; --r) {  // xloc /= subsampling, nlev times (:1352-1355)
+        xl = u(a.ss_inv != 0.0f ? xl * a.ss_inv : xl / a.ss);
+        yl = u(a.ss_inv != 0.0f ? yl * a.ss_inv : yl / a.ss);
+      }
+      float xo = xl, yo = yl;
+      int val = kTracked;
+      bool lost_prev = false;
+#pragma unroll
+      for (int r = nlev - 1; r >= 0; --r) {
+        xl = u(xl * a.ss);
+        yl = u(yl * a.ss);
+        xo = u(xo * a.ss);
+        yo = u(yo * a.ss);
+        const Lev LA = lev_prev(a, b, r, j);
+        const Lev LB = lev_of(a.B[r], (long)j * b.lfs[r], a.oobx[r], a.ooby[r]);
+        const bool lj = job && r == nlev - 1;
+        T7_T(t_l0);
+        val = level7<BAND, AOS, FAST>(a, LA, LB, xl, yl, xo, yo, lane, fi, fj, on, red, r == 0,
+                           merge && r == 0 && j + 1 < b.nframes, pd, lj, R, rstat, lost_prev, cnt);
+        T7_ADD(10, t_l0);
+        if (lost_prev) break;
+        if (val == kSmallDet || val == kOOB) break;
+      }
+      if (!lost_prev) {
+        const bool border = xo < a.borderx || xo > a.ncols - 1 - a.borderx || yo < a.bordery ||
+                            yo > a.nrows - 1 - a.bordery;
+        if (val == kOOB || border) {
+          pd.on = false;  // outside the border: OOB whatever the residue (trackFeatures.c:1383-1398)
+          x = -1.0f;
+          y = -1.0f;
+          v = kOOB;
+        } else if (val != kTracked) {
+          x = -1.0f;
+          y = -1.0f;
+          v = val;
+        } else {
+          x = xo;
+          y = yo;
+          v = kTracked;
+        }
+      }
+    }
+    if constexpr (FB) {
+      float e = -1.0f;  // no distance: lost before, by, or on the way back from this frame
+      if (v == kTracked) {
+        // KLTTrackFeatures(img2, img1) from the forward position: bank frame j is image 1
+        float xl = x, yl = y;
+#pragma unroll
+        for (int r = nlev - 1; r >= 0; --r) {
+          xl = u(a.ss_inv != 0.0f ? xl * a.ss_inv : xl / a.ss);
+          yl = u(a.ss_inv != 0.0f ? yl * a.ss_inv : yl / a.ss);
+        }
+        float xo = xl, yo = yl;
+        int vb = kTracked;
+        bool none = false;
+        const Lev R = lev_prev(a, b, 0, j);  // unused without a job
+#pragma unroll
+        for (int r = nlev - 1; r >= 0; --r) {
+          xl = u(xl * a.ss);
+          yl = u(yl * a.ss);
+          xo = u(xo * a.ss);
+          yo = u(yo * a.ss);
+          const Lev LA = lev_of(a.B[r], (long)j * b.lfs[r], a.oobx[r], a.ooby[r]);
+          const Lev LB = lev_prev(a, b, r, j);
+          vb = level7<false, AOS, false>(a, LA, LB, xl, yl, xo, yo, lane, fi, fj, on, red, r == 0, false, pd, false, R,
+                                         rstat, none, cnt);
+          if (vb == kSmallDet || vb == kOOB) break;
+        }
+        const bool border = xo < a.borderx || xo > a.ncols - 1 - a.borderx || yo < a.bordery ||
+                            yo > a.nrows - 1 - a.bordery;
+        bool rej = vb != kTracked || border;
+        if (!rej) {  // five float operations, each rounded (contraction is off in this file)
+          const float dx = xo - xp, dy = yo - yp;
+          const float dx2 = dx * dx, dy2 = dy * dy;
+          e = u(dx2 + dy2);
+          rej = e > fb.t2;
+        }
+        if (rej) {
+          x = -1.0f;
+          y = -1.0f;
+          v = kFbRejected;
+        }
+      }
+      if (fb.err && lane == 0) fb.err[j * fb.stride + f] = e;
+    }
+    if (job) {  // frame j-1's verdict came with frame j's first pass
+      if (rstat != kTracked) {
+        x = -1.0f;
+        y = -1.0f;
+        v = rstat;
+      }
+      if (b.tx && lane == 0) {
+        b.tx[(j - 1) * b.tstride + f] = rstat != kTracked ? -1.0f : xp;
+        b.ty[(j - 1) * b.tstride + f] = rstat != kTracked ? -1.0f : yp;
+        b.tv[(j - 1) * b.tstride + f] = rstat;
+      }
+    }
+    if (b.tx && lane == 0 && !pd.on) {
+      b.tx[j * b.tstride + f] = x;
+      b.ty[j * b.tstride + f] = y;
+      b.tv[j * b.tstride + f] = v;
+    }
+    T7_ADD(4, t_f0);
+  }
+#ifdef KLT_TRACK_PROF
+  cnt.c[5] = cnt.solves;
+  cnt.c[6] = cnt.passes;
+  cnt.c[8] = wall0;
+  cnt.c[9] = wall_clock64();
+  cnt.c[7] = cnt.c[9] - wall0;
+  if (b.prof && lane == 0)
+    for (int k = 0; k < kProfN; ++k) b.prof[(long)slot * kProfN + k] = cnt.c[k];
+#endif
+  if (lane == 0) {
+    fx[f] = x;
+    fy[f] = y;
+    fv[f] = v;
+    if (b.count) {
+      const int k = slot & (kCountSlots - 1);
+      atomicAdd(&b.count[k], (unsigned long long)cnt.solves);
+      atomicAdd(&b.count[kCountSlots + k], (unsigned long long)cnt.passes);
+    }
+  }

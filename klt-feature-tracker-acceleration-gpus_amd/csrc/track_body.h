@@ -1,0 +1,124 @@
+// track_body.h -- the body shared by k_track_frames_g and k_track_frames_g_fb
+// (track.hip), included inside each kernel: the FB-off kernels keep their
+// by-value arguments and compile to what they were before the
+// forward-backward instances existed.  The including kernel provides: the
+// template parameters G, PPL, PATCH, WIN, EXACT, LI, BAND; constexpr bool FB;
+// TrkArgs a; TrkFramesArgs b; TrkFbArgs fb; fx, fy, fv, n; and the LDS array
+// red_all.
+  if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  // consecutive workgroups land on the 8 XCDs round-robin: give each XCD a
+  // contiguous run of the (band-sorted) order so its L2 sees one image band
+  if (b.n_dev) n = *b.n_dev;
+  // band mode: the grid is sized for every feature, but only the n_dev kept
+  // ones are processed -- spread THEIR blocks over the 8 XCDs (a per-XCD run
+  // sized for all features would put a small band on one XCD)
+  const int xcd_per = b.n_dev && b.xcd_per > 0 ? ((n + kBlock / kWave * G - 1) / (kBlock / kWave * G) + 7) / 8
+                                                 : b.xcd_per;
+  if (xcd_per > 0 && (int)(blockIdx.x / 8) >= xcd_per) return;  // past this XCD's run: no duplicate slots
+  const int blk = xcd_per > 0 ? (int)(blockIdx.x % 8) * xcd_per + (int)(blockIdx.x / 8) : (int)blockIdx.x;
+  const int s0 = (blk * (kBlock / kWave) + wave) * G;
+  if (s0 >= n) return;  // whole wave; the kernel has no workgroup barrier
+  const int g = lane / LG, slot = s0 + g;
+  const bool exists = slot < n;
+  const int f = exists ? (b.perm ? b.perm[slot] : slot) : 0;
+  float x = 0.0f, y = 0.0f;
+  int v = -1;
+  if (exists) {
+    x = uni<G>(fx[f]);
+    y = uni<G>(fy[f]);
+    v = uni<G>(fv[f]);
+  }
+  const GroupWin<G, PPL, PATCH, WIN> w = group_window<G, PPL, PATCH, WIN>(a.ww, a.wh, lane);
+  {  // row pads of the ordered-sum staging stay +0 for the whole kernel
+    float *red = red_all[wave];
+    constexpr int RED = 6 * G * (LG * PPL + 4) + 16;
+    for (int i = lane; i < RED; i += kWave) red[i] = 0.0f;
+    lds_wave_sync();
+  }
+  const bool head = exists && (lane % LG) == 0;
+#ifdef KLT_TRACK_PROF
+  Prof prof;
+  const unsigned long long wall0 = wall_clock64();
+#endif
+  // deferred residues (ResCarry): one-feature waves, exact sums, default gain
+  // (band mode too: the residue's rows were checked against the band at frame
+  // j's final position, and an escape voids the whole chunk anyway)
+  const bool merge = !FB && G == 1 && EXACT && !LI && a.merge_res && a.nlev >= 2;
+  ResCarry<PPL> rc;
+  TrkCount cnt;
+  for (int j = 0; j < b.nframes; ++j) {
+    const bool job = rc.pending;  // frame j-1 is tentatively tracked at (x, y)
+    const bool live = exists && (v >= 0 || job);  // lost features are not tracked (:1346)
+    const float xp = x, yp = y;
+    int rstat = kTracked;
+    PROF_T(t_f0);
+    if (wave_any(live)) {
+      auto LA = [&](int r) { return j == 0 ? a.A[r] : at_frame(a.B[r], (long)(j - 1) * b.lfs[r]); };
+      track_feature_g<G, PPL, PATCH, WIN, EXACT, LI, BAND>(
+          PROF_ARG a, w, LA, [&](int r) { return at_frame(a.B[r], (long)j * b.lfs[r]); }, x, y, v, live, lane,
+          red_all[wave], rc, job, merge && j + 1 < b.nframes, LA(0), rstat, cnt);
+    }
+    if constexpr (FB) {
+      float e = -1.0f;  // no distance: lost before, by, or on the way back from this frame
+      const bool back = live && v == kTracked;
+      if (wave_any(back)) {
+        auto LA = [&](int r) { return j == 0 ? a.A[r] : at_frame(a.B[r], (long)(j - 1) * b.lfs[r]); };
+        float xb = x, yb = y;
+        int vb = v;
+        track_feature_g<G, PPL, PATCH, WIN, EXACT, LI, BAND>(
+            PROF_ARG a, w, [&](int r) { return at_frame(a.B[r], (long)j * b.lfs[r]); }, LA, xb, yb, vb, back, lane,
+            red_all[wave], rc, false, false, LA(0), rstat, cnt);
+        if (back) {
+          bool rej = vb != kTracked;
+          if (!rej) {  // five float operations, each rounded (contraction is off in this file)
+            const float dx = xb - xp, dy = yb - yp;
+            const float dx2 = dx * dx, dy2 = dy * dy;
+            e = uni<G>(dx2 + dy2);
+            rej = e > fb.t2;
+          }
+          if (rej) {
+            x = -1.0f;
+            y = -1.0f;
+            v = kFbRejected;
+          }
+        }
+      }
+      if (fb.err && head) fb.err[j * fb.stride + f] = e;
+    }
+    PROF_ADD(4, t_f0);
+    if (job) {  // frame j-1's verdict came with frame j's first pass
+      if (rstat != kTracked) {
+        x = -1.0f;
+        y = -1.0f;
+        v = rstat;
+      }
+      if (b.tx && head) {
+        b.tx[(j - 1) * b.tstride + f] = rstat != kTracked ? -1.0f : xp;
+        b.ty[(j - 1) * b.tstride + f] = rstat != kTracked ? -1.0f : yp;
+        b.tv[(j - 1) * b.tstride + f] = rstat;
+      }
+    }
+    if (b.tx && head && !rc.pending) {
+      b.tx[j * b.tstride + f] = x;
+      b.ty[j * b.tstride + f] = y;
+      b.tv[j * b.tstride + f] = v;
+    }
+  }
+  if (head) {
+    fx[f] = x;
+    fy[f] = y;
+    fv[f] = v;
+    if (b.count) {  // one pair of atomics per feature per launch, spread over kCountSlots addresses
+      const int k = (blk * (kBlock / kWave) + wave) & (kCountSlots - 1);
+      atomicAdd(&b.count[k], (unsigned long long)cnt.solves);
+      atomicAdd(&b.count[kCountSlots + k], (unsigned long long)cnt.passes);
+    }
+  }
+#ifdef KLT_TRACK_PROF
+  prof.c[8] = wall0;
+  prof.c[9] = wall_clock64();
+  prof.c[7] = prof.c[9] - wall0;  // constant-rate ticks over the wave's life
+  if (b.prof && lane == 0)
+    for (int k = 0; k < kProfN; ++k) b.prof[(long)(blk * (kBlock / kWave) + wave) * kProfN + k] = prof.c[k];
+#endif

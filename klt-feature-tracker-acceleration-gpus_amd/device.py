@@ -12,6 +12,7 @@ import os
 MAX_TAPS = 71
 MAX_LEVELS = 8
 EXACT, FAST = 0, 1
+FB_REJECTED = -6  # KLT_HIP_FB_REJECTED: lost to the forward-backward check (klt_hip_set_fb)
 
 
 class Taps(C.Structure):
@@ -69,6 +70,9 @@ DEVICE_PROTOS = {
     "klt_hip_set_track_prio": (C.c_int, [V, C.c_int]),
     "klt_hip_set_track_impl": (C.c_int, [V, C.c_int]),
     "klt_hip_set_track_patch": (C.c_int, [V, C.c_int]),
+    "klt_hip_set_fb": (C.c_int, [V, C.c_int, C.c_float]),
+    "klt_hip_get_fb": (C.c_int, [V, IP, FP]),
+    "klt_hip_set_fb_table": (C.c_int, [V, V, C.c_long]),
     "klt_hip_set_track_count": (C.c_int, [V, C.c_int]),
     "klt_hip_get_track_count": (C.c_int, [V, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_int]),
     "klt_hip_set_prof": (C.c_int, [V, V]),
@@ -144,6 +148,7 @@ DEVICE_PROTOS = {
     "klt_amd_pyr_desc": (None, [V, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PyrDesc)]),
     "klt_amd_track_desc": (None, [V, C.POINTER(TrackDesc)]),
     "klt_amd_set_reduction": (None, [V, C.c_int]),
+    "klt_amd_set_fb_check": (C.c_int, [V, C.c_int, C.c_float]),
     "klt_amd_release_cached_devices": (C.c_int, []),
     "klt_amd_register_buffer": (C.c_int, [V, V, C.c_size_t]),
     "klt_amd_unregister_buffer": (C.c_int, [V, V]),
