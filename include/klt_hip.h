@@ -145,6 +145,18 @@ int klt_hip_set_track_impl(klt_hip_ctx *ctx, int impl);
    verdict loses frame j's feature.  0: a residue pass of its own.  Results do
    not depend on it. */
 int klt_hip_set_track_merge(klt_hip_ctx *ctx, int on);
+/* 1 (default): a plain klt_hip_track_frames* call on the fused pyramid path,
+   tracked by the default 7x7 kernel (exact sums, or fast sums on a two-level
+   pyramid) with the forward-backward check off, keeps level 0 of its pyramid
+   banks as the image plane alone; the
+   tracker computes the level-0 gradients of the pixels its windows read, bit
+   for bit the pyramid kernels' values.  0: level 0 with its gradients for
+   every pixel, as every other call (band, forward-backward, other windows,
+   lighting-insensitive, the generic pyramid path, per-call tracking) builds it.  A later
+   reader of the kept pyramid that needs level-0 gradients (a call in another
+   layout, klt_hip_frames_end_slot, klt_hip_min_eigen_rows) first completes
+   that one frame.  Results do not depend on it.  klt_hip_ctx_reset restores 1. */
+int klt_hip_set_lazy_grad(klt_hip_ctx *ctx, int on);
 /* Forward-backward (FB) consistency check, off by default.  With it on, every
    tracked frame img1 -> img2 of klt_hip_track (host or device arrays),
    klt_hip_track_sequence, klt_hip_track_frames and klt_hip_track_frames_host

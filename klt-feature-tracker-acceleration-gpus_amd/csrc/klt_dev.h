@@ -78,6 +78,10 @@ __host__ __device__ __forceinline__ long hs_size(int W1, int H) {
 // consecutive registers (the pair is even-aligned), and a wave writes 64
 // consecutive records as one contiguous 768-byte run.
 constexpr int kRecGx = 0, kRecGy = 1, kRecImg = 2, kRec = 3;
+// A level's layout (Level::il / TrkLevel::il): three planes, the interleaved
+// records, or -- level 0 of a bank whose tracker computes its own windows'
+// gradients from the image (klt_hip_set_lazy_grad) -- the img plane alone
+constexpr int kLayoutPlanes = 0, kLayoutRec = 1, kLayoutImg = 2;
 
 // tile geometry the runtime needs for grids and band bookkeeping
 namespace geom {
@@ -97,7 +101,7 @@ struct TrkLevel {
   const float *img, *gx, *gy;  // il: img is the interleaved base ({gx, gy, img} per pixel), gx/gy null
   int w, h;
   int vlo = 0, vhi = 1 << 30;  // rows that hold valid data (a band-built pyramid: fewer)
-  int il = 0;
+  int il = 0;                  // kLayoutPlanes / kLayoutRec / kLayoutImg (img alone, gx/gy null)
 };
 
 struct TrkArgs {
@@ -120,6 +124,11 @@ struct TrkArgs {
   // float x >= 3 with (float)w - (x + 3) < 1.001f (ooby: the same for h), so the
   // window bounds test is integer compares of x's and y's bit patterns
   int oobx[KLT_HIP_MAX_LEVELS], ooby[KLT_HIP_MAX_LEVELS];
+  // k_track7's lazy-gradient instances: level 0 of B (and of A, when A[0].il
+  // says so) is an img plane, and the kernel computes the gradients of the
+  // pixels its windows touch with these taps (DefTaps::g / ::d, reversed)
+  int lazy;
+  float gg[7], gd[7];
 };
 
 // batched frames: frame j tracks pyramid j-1 -> j of a bank; row j of the
@@ -171,6 +180,7 @@ struct AffArgs {
 // k_pyr_l0 over F frames (src + f*stride; outputs + f*fs0, hs + f*fsh), level-0
 // tile rows [ty0, ty1) of 32-row tiles; only tile rows [py0, py1) store the
 // level-0 planes (the others only the sigma-3.6 rows pass, hs)
+// il: kLayoutPlanes, kLayoutRec, or kLayoutImg (img as a plane, no gradients)
 hipError_t launch_pyr_l0(hipStream_t st, const uint8_t *src, int pitch, long stride, int W, int H, const DefTaps &T,
                          int vec_u8, int vec_out, float *img, float *gx, float *gy, float *hs, int W1, int do_hs,
                          long fs0, long fsh, int F, int ty0, int ty1, int py0 = 0, int py1 = 1 << 30, int il = 0);
@@ -196,6 +206,8 @@ hipError_t launch_synth(hipStream_t st, unsigned long long seed, int t0, int n, 
 hipError_t launch_selftest_sqrt(const double *in, double *out, int n);
 // n pixels of an interleaved level into three planes
 hipError_t launch_from_il(hipStream_t st, const float *il, float *img, float *gx, float *gy, long n);
+// and back: n pixels of a plane into field kRecGx / kRecGy / kRecImg of {gx, gy, img} records
+hipError_t launch_to_il(hipStream_t st, const float *plane, float *il, int field, long n);
 // n 32-bit words, 16-byte aligned ends (device or mapped pinned host memory)
 hipError_t launch_copy_words(hipStream_t st, const void *src, void *dst, long n);
 hipError_t launch_selftest_div(const float *a, const float *b, float *out, int n);

@@ -104,14 +104,17 @@ __device__ __forceinline__ f4 mul4(const float *v, float k) {
 // wave per 8 tile rows in E): TH_ = 32 (256 threads; band builds, whose rows
 // are whole 32-row tiles) or 64 (512 threads; whole frames: fewer halo rows
 // recomputed per output row, LDS 61.6 KB, two workgroups per CU)
-template <int TH_>
+// HR_: the img0 halo rows computed above and below the tile -- kRG for the
+// gradient columns pass, 0 for the image-only instance (no gradients: fewer
+// staged rows, a smaller t1 and img0, and no tx/ty region)
+template <int TH_, int HR_ = kRG>
 struct L0G {
-  static constexpr int RS = kRS, RG = kRG, RP = kRP, SS = kSS, TW = geom::L0_TW, TH = TH_;
+  static constexpr int RS = kRS, RG = kRG, RP = kRP, SS = kSS, TW = geom::L0_TW, TH = TH_, HR = HR_;
   static constexpr int NT = 8 * TH;                // threads
   static constexpr int UQ = 24;                    // staged u8 dwords per row: global [C0-12, C0+84)
-  static constexpr int UH = TH + 2 * RG + 2 * RS + 2;  // staged rows: global R0-5 ..  (2 spare for 4-row blocks)
+  static constexpr int UH = TH + 2 * HR + 2 * RS + 2;  // staged rows: global R0-HR-RS ..  (2 spare for 4-row blocks)
   static constexpr int NG = 21;                    // 4-column groups of t1 / img0: global [C0-8, C0+76)
-  static constexpr int IH = TH + 2 * RG;           // img0 rows used (global R0-3 ..)
+  static constexpr int IH = TH + 2 * HR;           // img0 rows used (global R0-HR ..)
   static constexpr int IHB = (IH + 3) / 4;         // 4-row blocks of img0 computed
   // LDS pitches (floats) chosen with tools/lds_banks.py so that the 16-lane
   // groups of each ds_read_b128 hit (nearly) distinct bank slots; a few bank
@@ -120,12 +123,13 @@ struct L0G {
   static constexpr int PUB = 24;                   // staged u8 row pitch in dwords (96 bytes)
   static constexpr int U_WORDS = UH * PUB;
   static constexpr int REG_A = U_WORDS > IH * PI ? U_WORDS : IH * PI;  // u during A-B, then img0 during C-D
-  static constexpr int REG_B = 2 * IH * PX;                            // t1 during B-C, then tx|ty during D-E
+  // t1 during B-C, then tx|ty during D-E (the image-only instance: t1 alone)
+  static constexpr int REG_B = HR > 0 ? 2 * IH * PX : UH * PT;
   static constexpr int LDS = REG_A + REG_B;
   static constexpr int RB = NT / 11;               // B: rows per pass (11 eight-column groups a row)
   static constexpr int R16 = NT / 16;              // D: rows per pass (16 four-column groups a row)
   // interior tiles: one 16-byte chunk per thread covers the staged rows
-  static constexpr int NQ = UQ / 4, NR = TH + 2 * RG + 2 * RS;
+  static constexpr int NQ = UQ / 4, NR = TH + 2 * HR + 2 * RS;
   static_assert(IH * PI <= REG_A && UH * PT <= REG_B, "LDS aliasing");
   static_assert(TH % 16 == 0 && TW % 16 == 0 && TH * TW / 16 <= NT, "tile shape");
   static_assert(NR * NQ <= NT && NR <= UH, "one 16-byte load per thread");
@@ -176,15 +180,18 @@ __device__ unsigned long long *g_pyr_prof;
 // element; interior tiles (~90 % at 1080p, 94 % at 4K) need neither.
 // IL: the level's planes interleaved per pixel, {gx, gy, img} (12 bytes, klt_dev.h)
 // at img0 + 3*(y*W + x) -- written in E, where img0 is still in LDS; gx0/gy0 unused
-template <bool INT, bool IL, int TH_>
+// IMG (with IL false): the image-only instance -- phases A-C, img0 as a plane
+// (D1) and the sigma-3.6 rows pass (D3); no gradient passes, no halo rows
+template <bool INT, bool IL, int TH_, bool IMG = false>
 __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8_t *__restrict__ src, int spitch,
                                             int W, int H, const DefTaps &T, int vec_u8,
                                             float *__restrict__ img0, float *__restrict__ gx0,
                                             float *__restrict__ gy0, float *__restrict__ hs, int hsW,
                                             int do_hs, int vec_out, int C0, int R0, int tid, bool planes,
                                             bool cols_in, bool rows_in) {
-  using G = L0G<TH_>;
-  constexpr int RS = G::RS, RG = G::RG, RP = G::RP, SS = G::SS, TW = G::TW, TH = G::TH, NT = G::NT;
+  static_assert(!(IMG && IL), "the image-only instance stores a plane");
+  using G = L0G<TH_, IMG ? 0 : kRG>;
+  constexpr int RS = G::RS, RG = G::RG, RP = G::RP, SS = G::SS, TW = G::TW, TH = G::TH, NT = G::NT, HR = G::HR;
   constexpr int UQ = G::UQ, UH = G::UH, NG = G::NG, IH = G::IH, IHB = G::IHB, PT = G::PT, PI = G::PI, PX = G::PX,
                 PXY = G::PXY, PUB = G::PUB, REG_A = G::REG_A, NQ = G::NQ, NR = G::NR, RB = G::RB, R16 = G::R16;
   float *u = lds;            // [UH][PUB] staged bytes
@@ -205,7 +212,7 @@ __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8
     // loads stay branch-free.
     const int i = min(tid, NR * NQ - 1);
     const int r = i / NQ, q = i - r * NQ;
-    const uint4 c = *reinterpret_cast<const uint4 *>(src + (unsigned)((R0 - RG - RS + r) * spitch + C0 - 12 + 16 * q));
+    const uint4 c = *reinterpret_cast<const uint4 *>(src + (unsigned)((R0 - HR - RS + r) * spitch + C0 - 12 + 16 * q));
     *reinterpret_cast<uint4 *>(reinterpret_cast<uint32_t *>(u) + r * PUB + 4 * q) = c;
   } else if (vec_u8) {
     // edge tile: the interior's one 16-byte chunk per thread (the same rows),
@@ -217,7 +224,7 @@ __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8
     // frame; every in-frame dword (W % 4 == 0 under vec_u8) is exact
     const int i = min(tid, NR * NQ - 1);
     const int r = i / NQ, q = i - r * NQ;
-    const uint8_t *row = src + (unsigned)(clampi(R0 - RG - RS + r, 0, H - 1) * spitch);
+    const uint8_t *row = src + (unsigned)(clampi(R0 - HR - RS + r, 0, H - 1) * spitch);
     const int x = C0 - 12 + 16 * q;
     uint4 c;
     if (x >= 0 && x + 16 <= W) {
@@ -240,7 +247,7 @@ __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8
       const int i = min(tid + k * NT, NA - 1);
       const int r = i / UQ, q = i - r * UQ;
       const int x = C0 - 12 + 4 * q;
-      const unsigned rowp = (unsigned)(clampi(R0 - RG - RS + r, 0, H - 1) * spitch);
+      const unsigned rowp = (unsigned)(clampi(R0 - HR - RS + r, 0, H - 1) * spitch);
       if (vec_u8) {
         w[k] = *reinterpret_cast<const uint32_t *>(src + rowp + clampi(x, 0, W - 4));
       } else {
@@ -314,7 +321,7 @@ __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8
 #pragma unroll
       for (int m = 1; m < 5; ++m) mac4(acc, reinterpret_cast<const float *>(&v[rr + m]), T.s[m]);
       if (!INT && !rows_in) {
-        const int y = R0 - RG + 4 * b + rr;
+        const int y = R0 - HR + 4 * b + rr;
         if (!(y >= RS && y < H - RS)) acc = f4{0.0f, 0.0f, 0.0f, 0.0f};
       }
       if (IH % 4 == 0 || 4 * b + rr < IH) st4(im + (4 * b + rr) * PI + 4 * g, acc);  // rows >= IH unused
@@ -331,7 +338,7 @@ __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8
     if (!planes || IL) break;
     const int r = r16 + R16 * k, g = g16;
     const int y = R0 + r, x = C0 + 4 * g;
-    const f4 val = ld4(im + (r + RG) * PI + 8 + 4 * g);
+    const f4 val = ld4(im + (r + HR) * PI + 8 + 4 * g);
     if (INT) {
       st4_out(img0 + (unsigned)(y * W + x), val);
     } else {
@@ -346,7 +353,7 @@ __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8
 #pragma unroll
   for (int k = 0; k < (IH + R16 - 1) / R16; ++k) {
     const int r = r16 + R16 * k, g = g16;
-    if (r >= IH || !planes) break;
+    if (IMG || r >= IH || !planes) break;
     const float *row = im + r * PI + 4 * g + 4;  // img0 idx c0+4 <-> global C0+c0-4
     float v[12];
     *reinterpret_cast<f4 *>(v) = ld4(row);
@@ -409,7 +416,7 @@ __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8
   if (do_hs && tid >= NT - TH * (TW / 16)) {
     const int i = tid - (NT - TH * (TW / 16));
     const int r = i / (TW / 16), q = i - r * (TW / 16);
-    const float *row = im + (r + RG) * PI + 16 * q;  // idx 16q <-> global C0+16q-8
+    const float *row = im + (r + HR) * PI + 16 * q;  // idx 16q <-> global C0+16q-8
     float v[36];
 #pragma unroll
     for (int k = 0; k < 9; ++k) *reinterpret_cast<f4 *>(v + 4 * k) = ld4(row + 4 * k);
@@ -442,6 +449,10 @@ __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8
           if (X + e < hsW) hs[hs_at32(y, X + e, H)] = o[e];
       }
     }
+  }
+  if constexpr (IMG) {  // nothing reads LDS after D: no barrier, no E
+    PYR_END()
+    return;
   }
   __syncthreads();
   PYR_STAMP(4)
@@ -559,14 +570,14 @@ __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8
   PYR_END()
 }
 
-template <bool IL, int TH_>
+template <bool IL, int TH_, bool IMG = false>
 __global__ __launch_bounds__(L0G<TH_>::NT) void k_pyr_l0(const uint8_t *__restrict__ src, int spitch, int W, int H,
                                                    DefTaps T, int vec_u8, float *__restrict__ img0,
                                                    float *__restrict__ gx0, float *__restrict__ gy0,
                                                    float *__restrict__ hs, int hsW, int do_hs, int vec_out,
                                                    long fs_src, long fs0, long fs_hs, int ty0, int tiles_x,
                                                    int tiles_y, int py0, int py1) {
-  using G = L0G<TH_>;
+  using G = L0G<TH_, IMG ? 0 : kRG>;
   __shared__ __attribute__((aligned(16))) float lds[G::LDS];
   int bx, by;
   if (!xcd_tile(tiles_x, tiles_y, bx, by)) return;  // whole workgroup: no barrier is skipped
@@ -588,10 +599,10 @@ __global__ __launch_bounds__(L0G<TH_>::NT) void k_pyr_l0(const uint8_t *__restri
   const bool interior = vec_u8 && vec_out && (hsW * G::SS == W) && (hsW % 2 == 0) && cols_in && rows_in;
   const bool planes = by + ty0 >= py0 && by + ty0 < py1;  // tile rows [py0, py1) store img0, gx0, gy0
   if (interior)
-    pyr_l0_tile<true, IL, TH_>(lds, src, spitch, W, H, T, vec_u8, img0, gx0, gy0, hs, hsW, do_hs, vec_out, C0, R0,
+    pyr_l0_tile<true, IL, TH_, IMG>(lds, src, spitch, W, H, T, vec_u8, img0, gx0, gy0, hs, hsW, do_hs, vec_out, C0, R0,
                                threadIdx.x, planes, true, true);
   else
-    pyr_l0_tile<false, IL, TH_>(lds, src, spitch, W, H, T, vec_u8, img0, gx0, gy0, hs, hsW, do_hs, vec_out, C0, R0,
+    pyr_l0_tile<false, IL, TH_, IMG>(lds, src, spitch, W, H, T, vec_u8, img0, gx0, gy0, hs, hsW, do_hs, vec_out, C0, R0,
                                 threadIdx.x, planes, cols_in, rows_in);
 }
 
@@ -986,6 +997,14 @@ __global__ __launch_bounds__(kBlock) void k_from_il(const float *__restrict__ il
   gy[i] = il[kRec * i + kRecGy];
 }
 
+// a plane into one field of {gx, gy, img} records (a kept image-only frame made whole)
+__global__ __launch_bounds__(kBlock) void k_to_il(const float *__restrict__ plane, float *__restrict__ il, int field,
+                                                  long n) {
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  il[kRec * i + field] = plane[i];
+}
+
 // n 32-bit words from src to dst (16-byte aligned), 16 bytes per thread; one
 // side may be mapped pinned host memory (the per-call feature list)
 __global__ __launch_bounds__(kBlock) void k_copy_words(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst,
@@ -1041,7 +1060,10 @@ hipError_t launch_pyr_l0(hipStream_t st, const uint8_t *src, int pitch, long str
   if (l0_wide() && H >= kL0WideMinRows && ty0 == 0 && ty1 == nty && py0 == 0 && py1 >= nty) {
     using G = L0G<64>;
     const int ty = (H + G::TH - 1) / G::TH;
-    if (il)
+    if (il == kLayoutImg)
+      hipLaunchKernelGGL((k_pyr_l0<false, 64, true>), dim3(xcd_grid(tx * ty), 1, F), dim3(G::NT), 0, st, src, pitch, W,
+                         H, T, vec_u8, img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
+    else if (il)
       hipLaunchKernelGGL((k_pyr_l0<true, 64>), dim3(xcd_grid(tx * ty), 1, F), dim3(G::NT), 0, st, src, pitch, W, H, T,
                          vec_u8, img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
     else
@@ -1050,7 +1072,11 @@ hipError_t launch_pyr_l0(hipStream_t st, const uint8_t *src, int pitch, long str
     return hipGetLastError();
   }
   using G = l0::G32;
-  if (il)
+  if (il == kLayoutImg)
+    hipLaunchKernelGGL((k_pyr_l0<false, 32, true>), dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(G::NT), 0, st, src,
+                       pitch, W, H, T, vec_u8, img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0,
+                       py0, py1);
+  else if (il)
     hipLaunchKernelGGL((k_pyr_l0<true, 32>), dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(G::NT), 0, st, src, pitch, W,
                        H, T, vec_u8, img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0, py0, py1);
   else
@@ -1151,6 +1177,12 @@ hipError_t launch_copy_words(hipStream_t st, const void *src, void *dst, long n)
 hipError_t launch_from_il(hipStream_t st, const float *il, float *img, float *gx, float *gy, long n) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_from_il, dim3(blocks_for(n)), dim3(kBlock), 0, st, il, img, gx, gy, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_to_il(hipStream_t st, const float *plane, float *il, int field, long n) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_to_il, dim3(blocks_for(n)), dim3(kBlock), 0, st, plane, il, field, n);
   return hipGetLastError();
 }
 

@@ -26,6 +26,11 @@
 
 #define KLT_API extern "C" __attribute__((visibility("default")))
 
+// klt_hip_set_lazy_grad's default ("Level-0 gradients in the tracker")
+#ifndef KLT_LAZY_GRAD_DEFAULT
+#define KLT_LAZY_GRAD_DEFAULT 1
+#endif
+
 using namespace kltdev;
 
 // ===========================================================================
@@ -39,13 +44,14 @@ struct Level {
   int w = 0, h = 0;
   float *img = nullptr, *gx = nullptr, *gy = nullptr;  // gx = img + cap, gy = img + 2 cap
   size_t cap = 0;  // floats per plane
-  int il = 0;      // contents interleaved
+  int il = 0;      // contents: kLayoutPlanes, kLayoutRec (interleaved) or kLayoutImg (the img plane alone)
 };
 
 // a slot's level, or frame f of a bank's (interleaved levels: img is the
 // frame's interleaved base, gx/gy null)
 static TrkLevel level_view(const Level &L, long f = 0, int vlo = 0, int vhi = 1 << 30) {
   const long n = (long)L.w * L.h;
+  if (L.il == kLayoutImg) return TrkLevel{L.img + f * n, nullptr, nullptr, L.w, L.h, vlo, vhi, kLayoutImg};
   if (L.il) return TrkLevel{L.img + 3 * f * n, nullptr, nullptr, L.w, L.h, vlo, vhi, 1};
   return TrkLevel{L.img + f * n, L.gx + f * n, L.gy + f * n, L.w, L.h, vlo, vhi, 0};
 }
@@ -301,6 +307,8 @@ struct klt_hip_ctx {
   int track_order = 0;  // 0: band-sorted, XCD-major processing order; 1: input order
   int track_patch = 1;  // one-feature waves gather through a lane patch when the window fits
   int track_merge = 1;   // defer finest-level residues into the next frame's first pass (ResCarry)
+  int lazy_grad = KLT_LAZY_GRAD_DEFAULT;  // klt_hip_set_lazy_grad: image-only level 0 in the banks of plain batched calls
+  RTaps lazy_gg, lazy_gd;  // the gradient taps of the last such call (a kept image-only frame is made whole with them)
   int track_prio = 1;    // tracker waves at issue priority 3 (klt_hip_set_track_prio)
   // planes of interleaved levels for the kernels that read planes (the generic
   // tracker, the affine check): [0] image 1, [1] image 2 (a batch of frames)
@@ -1132,14 +1140,17 @@ int build_fused_bank_range(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, c
   int p0 = clampi(plane_lo, 0, H), p1 = plane_hi >= H ? H : clampi(plane_hi, p0, H);
   // il: interleaved (frame f at img + 3 f w h); else planes (frame f at
   // img / gx / gy + f w h), for a batch that a planes-reading tracker takes
-  const int np = il ? 3 : 1;
-  for (int l = 0; l < d->nlevels; ++l) K.lv[l].il = il;
+  // kLayoutImg: level 0 the img plane alone (frame f at img + f w h), the
+  // levels above interleaved
+  const int il1 = il == kLayoutImg ? kLayoutRec : il;
+  const int np0 = il == kLayoutRec ? 3 : 1, np = il1 ? 3 : 1;
+  for (int l = 0; l < d->nlevels; ++l) K.lv[l].il = l == 0 ? il : il1;
   auto at = [](float *p, long off) { return p ? p + off : p; };
-  const long o0 = (long)f0 * np * fs0, oh = (long)f0 * fsh, o1 = (long)f0 * np * fs1;
+  const long o0 = (long)f0 * np0 * fs0, oh = (long)f0 * fsh, o1 = (long)f0 * np * fs1;
   {
     TimedScope ts(c, T_L0, st, F);
     if (launch_l0(c, st, src, pitch, stride, W, H, T, vec_u8, vec_out, at(K.lv[0].img, o0), at(K.lv[0].gx, o0),
-                  at(K.lv[0].gy, o0), at(K.hs, oh), W1, (two && W1 > 0) ? 1 : 0, np * fs0, fsh, F, r0, r1, &p0, &p1,
+                  at(K.lv[0].gy, o0), at(K.hs, oh), W1, (two && W1 > 0) ? 1 : 0, np0 * fs0, fsh, F, r0, r1, &p0, &p1,
                   il))
       return -1;
   }
@@ -1164,7 +1175,7 @@ int build_fused_bank_range(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, c
       const int vec = (W1 % 4 == 0 && W1 >= 8) ? 1 : 0;
       if (launched(c, "k_pyr_l1", launch_pyr_l1(st, at(K.hs, oh), W1, H, H1, T, vec, at(K.lv[1].img, o1),
                                                 at(K.lv[1].gx, o1), at(K.lv[1].gy, o1), fsh, np * fs1, F, t1lo, t1hi,
-                                                il)))
+                                                il1)))
         return -1;
       HMARK_IN("l1_launched");
     }
@@ -1428,6 +1439,7 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->track_order = 0;
   c->track_patch = 1;
   c->track_merge = 1;
+  c->lazy_grad = KLT_LAZY_GRAD_DEFAULT;
   c->track_prio = 1;
   c->track_impl = 0;
   c->fb_on = 0;
@@ -1723,6 +1735,12 @@ KLT_API int klt_hip_set_track_patch(klt_hip_ctx *c, int on) {
   return 0;
 }
 
+
+KLT_API int klt_hip_set_lazy_grad(klt_hip_ctx *c, int on) {
+  if (!c) return fail(c, "set_lazy_grad: null context");
+  c->lazy_grad = on ? 1 : 0;
+  return 0;
+}
 
 KLT_API int klt_hip_set_track_merge(klt_hip_ctx *c, int on) {
   if (!c) return fail(c, "set_track_merge: null context");
@@ -2177,6 +2195,52 @@ int copy_level(klt_hip_ctx *c, const TrkLevel &from, Level &to, long f, hipStrea
   }
   return 0;
 }
+
+// The kept pyramid made whole.  After a call whose banks hold level 0 as the
+// img plane alone (klt_hip_set_lazy_grad) the previous pyramid has no level-0
+// gradients; a reader that needs them -- a call in another layout, the copy
+// into a slot, the selection map -- first gets that one frame as a full
+// pyramid in the seed slot: level 0's gx / gy from its img with the generic
+// row and column kernels (the same values as the fused kernels', bit for bit:
+// tests/test_gpu_pyramid.py), interleaved into records like a fused slot's,
+// the levels above copied.  On the tracking stream, which has already waited
+// for the bank's build.
+int prev_full(klt_hip_ctx *c) {
+  if (c->prev.bank < 0) return 0;  // slots always hold whole levels
+  const Bank &K = c->bank[c->prev.bank];
+  if (K.lv[0].il != kLayoutImg) return 0;
+  const TrkLevel p0 = prev_level(c, 0);
+  klt_hip_pyr_desc d;
+  memset(&d, 0, sizeof d);
+  d.ncols = p0.w;
+  d.nrows = p0.h;
+  d.nlevels = K.nlev;
+  d.subsampling = K.ss > 1 ? K.ss : 2;
+  if (ensure_slot(c, kSeedSlot, &d)) return -1;
+  Slot &S = c->slot[kSeedSlot];
+  S.ss = K.ss;
+  S.fused = 1;
+  hipStream_t st = c->stream;
+  const long n0 = (long)p0.w * p0.h;
+  if (n0 > 0) {
+    if (grow(c, &c->d_tmp[0], &c->tmp_cap[0], (size_t)n0)) return -1;
+    if (grow(c, &c->d_tmp[1], &c->tmp_cap[1], (size_t)n0)) return -1;
+    float *t0 = c->d_tmp[0], *t1 = c->d_tmp[1], *rec = S.lv[0].img;
+    if (launched(c, "k_to_il", launch_to_il(st, p0.img, rec, kRecImg, n0)) ||
+        launched(c, "k_rows", launch_rows(st, p0.img, p0.w, p0.h, c->lazy_gd, t0)) ||
+        launched(c, "k_cols", launch_cols(st, t0, p0.w, p0.h, c->lazy_gg, t1)) ||
+        launched(c, "k_to_il", launch_to_il(st, t1, rec, kRecGx, n0)) ||
+        launched(c, "k_rows", launch_rows(st, p0.img, p0.w, p0.h, c->lazy_gg, t0)) ||
+        launched(c, "k_cols", launch_cols(st, t0, p0.w, p0.h, c->lazy_gd, t1)) ||
+        launched(c, "k_to_il", launch_to_il(st, t1, rec, kRecGy, n0)))
+      return -1;
+  }
+  S.lv[0].il = kLayoutRec;
+  for (int l = 1; l < K.nlev; ++l)
+    if (copy_level(c, prev_level(c, l), S.lv[l], 0, st)) return -1;
+  c->prev = PrevRef{-1, 0, kSeedSlot};
+  return 0;
+}
 }  // namespace
 
 KLT_API int klt_hip_frames_begin(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const unsigned char *frame,
@@ -2204,6 +2268,7 @@ KLT_API int klt_hip_frames_end_slot(klt_hip_ctx *c, int slot) {
   if (!c->frames_ready) return fail(c, "frames_end_slot: no current pyramid");
   if (c->prev.bank < 0 && c->prev.slot == slot) return 0;
   if (use_device(c)) return -1;
+  if (prev_full(c)) return -1;  // an image-only bank frame: whole in the seed slot first
   const int nl = c->prev.bank < 0 ? c->slot[c->prev.slot].nlev : c->bank[c->prev.bank].nlev;
   const int ss = c->prev.bank < 0 ? c->slot[c->prev.slot].ss : c->bank[c->prev.bank].ss;
   const TrkLevel p0 = prev_level(c, 0);
@@ -2282,6 +2347,16 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
   HMARK("checks");
   if (use_device(c)) return -1;
   HMARK("set_device");
+  const bool fz = fused_ok(pd) && !c->force_generic;
+  // level 0 of the banks as the img plane alone, its gradients computed by the
+  // tracker for the windows it reads (klt_hip_set_lazy_grad): whole-frame fused
+  // pyramids tracked by k_track7 (its fast-sum instance: two levels) without
+  // the forward-backward check, from a previous pyramid that is interleaved
+  // or image-only itself.  Any other call first makes an image-only previous
+  // pyramid whole.
+  const bool lazy = c->lazy_grad && fz && t7_tracks(c, td) && !band && !c->fb_on &&
+                    (td->reduction == KLT_HIP_EXACT || pd->nlevels == 2) && prev_level(c, 0).il != kLayoutPlanes;
+  if (!lazy && prev_full(c)) return -1;
   if (!c->pstream) {
     HIPCHK(c, make_pstream(c));
     HIPCHK(c, hipEventCreateWithFlags(&c->ev_start, hipEventDisableTiming));
@@ -2320,6 +2395,7 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
         bank_fits(c->bank[2], pd, chunk))) {
     // (re)allocation: drain both streams; a previous pyramid living in a bank
     // moves to the seed slot first
+    if (prev_full(c)) return -1;  // an image-only frame: whole, in the seed slot (drained below)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipStreamSynchronize(c->pstream));
     if (c->prev.bank >= 0) {
@@ -2363,13 +2439,22 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
   };
   if (!serial && !ahead) HIPCHK(c, hipEventRecord(c->ev_start, c->stream));
   if (!ahead && pstream_behind()) return -1;
-  const bool fz = fused_ok(pd) && !c->force_generic;
   if (band && !fz) return fail(c, "track_frames_band: needs the fused (default-parameter) pyramid path");
-  // the banks' layout follows their reader: interleaved for k_track7, planes
-  // for the generic tracker (no per-chunk conversion)
-  const int bil = t7_tracks(c, td) ? 1 : 0;
+  // the banks' layout follows their reader: interleaved for k_track7 (level 0
+  // the img plane alone for its lazy-gradient instance), planes for the
+  // generic tracker (no per-chunk conversion)
+  const int bil = lazy ? kLayoutImg : t7_tracks(c, td) ? kLayoutRec : kLayoutPlanes;
   TrkArgs a;
   fill_trk_args(td, pd->nlevels, pd->nlevels > 1 ? pd->subsampling : 1, pd->ncols, pd->nrows, a);
+  if (lazy) {
+    c->lazy_gg = reverse_taps(pd->grad_gauss);
+    c->lazy_gd = reverse_taps(pd->grad_deriv);
+    a.lazy = 1;
+    for (int m = 0; m < 2 * kRG + 1; ++m) {
+      a.gg[m] = c->lazy_gg.k[m];
+      a.gd[m] = c->lazy_gd.k[m];
+    }
+  }
   if (band) a.escape = band->escape;
   for (int j0 = 0; j0 < nframes; j0 += F) {
     const int Fc = F < nframes - j0 ? F : nframes - j0;
@@ -2422,7 +2507,7 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
     for (int l = 0; l < pd->nlevels; ++l) {
       a.A[l] = prev_level(c, l);
       a.B[l] = level_view(K.lv[l], 0, fz ? K.vlo[l] : 0, fz ? K.vhi[l] : (1 << 30));
-      b.lfs[l] = (long)K.lv[l].w * K.lv[l].h * (K.lv[l].il ? 3 : 1);
+      b.lfs[l] = (long)K.lv[l].w * K.lv[l].h * (K.lv[l].il == kLayoutRec ? 3 : 1);
     }
     b.nframes = Fc;
     if (ntab) {
@@ -2787,6 +2872,8 @@ KLT_API int klt_hip_min_eigen_rows(klt_hip_ctx *c, const klt_hip_select_desc *d,
                                    int *dev_map, int *nx, int *ny, int *r0, int *r1) {
   if (!c || !d || !nx || !ny || !r0 || !r1) return fail(c, "min_eigen_rows: null argument");
   if (!c->frames_ready) return fail(c, "min_eigen_rows: no tracked frame (call klt_hip_frames_begin)");
+  if (c->prev.bank >= 0 && c->bank[c->prev.bank].lv[0].il == kLayoutImg && (use_device(c) || prev_full(c)))
+    return -1;  // the map reads level-0 gradients
   const TrkLevel L = prev_level(c, 0);
   const int hw = d->window_width / 2, hh = d->window_height / 2;
   const int step = d->nSkippedPixels + 1;

@@ -267,14 +267,124 @@ __device__ __forceinline__ void sums(float *red, int lane, bool on, const float 
   else sums7<NS>(red, lane, on, v, out);
 }
 
+// ---------------------------------------------------------------------------
+// Lazy level-0 gradients (klt_hip_set_lazy_grad): the level is the img plane
+// alone and the wave computes gx / gy of the pixels its window touches, bit
+// for bit as the pyramid kernels do (pyramid.hip k_rows / k_cols and
+// pyr_l0_tile): tx = rows_d(img), ty = rows_g(img), gx = cols_g(tx),
+// gy = cols_d(ty), every sum from +0 over all seven taps in tap order, one
+// rounding per operation, and +0 within kHw pixels of a frame edge (the
+// passes' zero borders; every other pixel reads only in-frame values).
+//
+// A window at (x, y) has lane p's top-left corner at ((int)(x + i), (int)(y + j)),
+// i, j in -3..3.  With X0 = (int)(x - 3) (exact: x >= 3) that is X0 + i + 3, or
+// one more when the float sum x + i rounds up to the next integer -- and then
+// the lane's fraction is exactly 0, so its right-hand corners carry weight +0.
+// So the corners with a non-zero weight lie in the 8 x 8 block from (X0, Y0),
+// whose gradients read tx / ty on 14 rows x 8 columns, which read the 14 x 14
+// img block from (X0 - 3, Y0 - 3).  A corner index past the block (weight +0
+// only) is clamped into it: the product is a zero either way, and a zero's
+// sign changes no ordered sum, which start from +0, nor the residue's |.|.
+//
+// Per wave in LDS, one patch at a time: S, the img block (16 rows of pitch kPS,
+// two spare rows and columns loaded like the rest from clamped addresses); T,
+// {tx, ty} of 16 x 8; G, {gx, gy} of 8 x 8, over S once the rows pass has read
+// it (the lane's img corners are taken from S before).  Hand-offs are
+// wave-scope (wave_lds_sync).  2.5 KB per wave keeps a workgroup at 15 KB, so
+// that pyramid workgroups of an overlapped build still fit beside five
+// tracker workgroups per CU.
+// ---------------------------------------------------------------------------
+constexpr int kPS = 24;                                   // S pitch: the rows pass's 32-lane groups hit distinct banks
+constexpr int kPatS = 16 * kPS, kPatT = 2 * 16 * 8, kPatG = 2 * 8 * 8;
+constexpr int kPat = kPatS + kPatT;                       // floats per wave (640)
+static_assert(kPatG <= kPatS, "G over S");
+constexpr int kRedF = kRows * kRow + 4;                   // floats of a wave's ordered-sum rows
+
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+// this lane's four pixels of the staged block, rows sr + 4k of column sc; all
+// four loads are issued here, clamped into the frame
+__device__ __forceinline__ void patch_load(const float *img, int w, int h, int X0, int Y0, int lane, float (&v)[4]) {
+  const int sc = lane & 15, sr = 2 * ((lane >> 4) & 1) + (lane >> 5);
+  const unsigned xc = (unsigned)clampi(X0 - kHw + sc, 0, w - 1);
+  const char *b = reinterpret_cast<const char *>(img);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const unsigned yc = (unsigned)clampi(Y0 - kHw + sr + 4 * k, 0, h - 1);
+    v[k] = *reinterpret_cast<const float *>(b + (yc * (unsigned)w + xc) * 4u);
+  }
+}
+
+// One patch: v the lane's staged pixels (patch_load), cx / cy this lane's
+// corner column and row in the 8 x 8 block (0..7).  Out: the lane's corners of
+// img, gx, gy.
+__device__ __forceinline__ void patch_grads(float *pat, int lane, const TrkArgs &a, int w, int h, const float (&v)[4],
+                                            int X0, int Y0, int cx, int cy, Quad &qi, Quad &qx, Quad &qy) {
+  const int sc = lane & 15, sr = 2 * ((lane >> 4) & 1) + (lane >> 5);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) pat[(sr + 4 * k) * kPS + sc] = v[k];
+  wave_lds_sync();
+  {
+    const float *S = pat + (cy + kHw) * kPS + cx + kHw;  // the block's 14 columns hold cx + 1 <= 8
+    qi.r0 = make_float2(S[0], S[1]);
+    qi.r1 = make_float2(S[kPS], S[kPS + 1]);
+  }
+  // rows pass: {tx, ty} of block rows r and r + 8 (rows 14 and 15 are spare), column c = pixel X0 + c
+  const int c = lane & 7, r = lane >> 3;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const float *row = pat + (r + 8 * k) * kPS + c;
+    f2 t = {0.0f, 0.0f};
+#pragma unroll
+    for (int m = 0; m < 7; ++m) t += f2{row[m], row[m]} * f2{a.gd[m], a.gg[m]};
+    *reinterpret_cast<f2 *>(pat + kPatS + 2 * ((r + 8 * k) * 8 + c)) = t;
+  }
+  wave_lds_sync();
+  // columns pass: {gx, gy} of pixel (X0 + c, Y0 + r) from T rows r .. r + 6; G goes over S
+  {
+    const float *col = pat + kPatS + 2 * (r * 8 + c);
+    f2 g = {0.0f, 0.0f};
+#pragma unroll
+    for (int m = 0; m < 7; ++m) g += *reinterpret_cast<const f2 *>(col + 16 * m) * f2{a.gg[m], a.gd[m]};
+    const int x = X0 + c, y = Y0 + r;
+    if (x < kHw || x >= w - kHw || y < kHw || y >= h - kHw) g = f2{0.0f, 0.0f};
+    *reinterpret_cast<f2 *>(pat + 2 * (r * 8 + c)) = g;
+  }
+  wave_lds_sync();
+  const int cx1 = min(cx + 1, 7), cy1 = min(cy + 1, 7);
+  const f2 g00 = *reinterpret_cast<const f2 *>(pat + 2 * (cy * 8 + cx));
+  const f2 g01 = *reinterpret_cast<const f2 *>(pat + 2 * (cy * 8 + cx1));
+  const f2 g10 = *reinterpret_cast<const f2 *>(pat + 2 * (cy1 * 8 + cx));
+  const f2 g11 = *reinterpret_cast<const f2 *>(pat + 2 * (cy1 * 8 + cx1));
+  qx.r0 = make_float2(g00.x, g01.x);
+  qx.r1 = make_float2(g10.x, g11.x);
+  qy.r0 = make_float2(g00.y, g01.y);
+  qy.r1 = make_float2(g10.y, g11.y);
+  wave_lds_sync();  // the patch area is rewritten by the next patch
+}
+
+// The last level-0 pass's image-2 corners of a frame, kept for the next frame
+// (lazy-gradient instances): frame j's image 2 is frame j + 1's image 1, and
+// frame j + 1 starts where frame j ended, mostly in the same cell -- its
+// image-1 corners are then these, and no image-1 patch is computed.  px: the
+// corners' pixel per lane, ~0u when nothing is kept.
+struct Carry {
+  unsigned px = ~0u;
+  Quad i, x, y;
+};
+#ifndef KLT_T7_CARRY
+#define KLT_T7_CARRY 1  // A/B hook: 0 computes every first pass's image-1 patch
+#endif
+
 struct Lev {
   const float *img, *gx, *gy;
   int w, h, vlo, vhi;
   int tx, ty;  // out7's thresholds for this level's size (TrkArgs::oobx / ooby)
+  int il;      // the level's layout (klt_dev.h kLayout*); read by the lazy-gradient instances only
 };
 
 __device__ __forceinline__ Lev lev_of(const TrkLevel &L, long off, int tx, int ty) {
-  return Lev{L.img + off, L.gx + off, L.gy + off, L.w, L.h, L.vlo, L.vhi, tx, ty};
+  return Lev{L.img + off, L.gx + off, L.gy + off, L.w, L.h, L.vlo, L.vhi, tx, ty, L.il};
 }
 
 // image 1 of frame j at level r: the previous pyramid (a.A) for the batch's
@@ -286,7 +396,7 @@ __device__ __forceinline__ Lev lev_prev(const TrkArgs &a, const TrkFramesArgs &b
   const bool f = j == 0;
   const long off = f ? 0L : (long)(j - 1) * b.lfs[r];
   return Lev{(f ? P.img : Q.img) + off, (f ? P.gx : Q.gx) + off, (f ? P.gy : Q.gy) + off, f ? P.w : Q.w,
-             f ? P.h : Q.h, f ? P.vlo : Q.vlo, f ? P.vhi : Q.vhi, a.oobx[r], a.ooby[r]};
+             f ? P.h : Q.h, f ? P.vlo : Q.vlo, f ? P.vhi : Q.vhi, a.oobx[r], a.ooby[r], f ? P.il : Q.il};
 }
 
 // band-built pyramids (klt_hip_track_frames_band): every row the window's
@@ -339,10 +449,15 @@ enum { kPassAgain = 0, kPassDone = 1, kPassOOB = 2, kPassLostPrev = 3 };
 // level's FIRST pass; the deferred residue's img2 plane with a JOB), the
 // ordered sums, the solve.  Separate instances for the first pass and the
 // rest keep the first pass's addresses out of the loop.
-template <bool BAND, bool FIRST, bool JOB, bool AOS, bool FAST>
+// LZ (the lazy-gradient instances, AOS): 1 a level above 0, interleaved like
+// any AOS level; 2 level 0, image 2 the img plane alone and image 1 that or
+// (the launch's first frame, from a whole previous pyramid) interleaved.  In
+// both the deferred residue's level 0 (R: a bank frame) is the img plane.
+template <bool BAND, bool FIRST, bool JOB, bool AOS, bool FAST, int LZ = 0>
 __device__ __forceinline__ int pass7(const TrkArgs &a, const Lev &A, const Lev &B, float x1, float y1, bool x1_out,
                                      LevState &ls, int lane, float fi, float fj, bool on, float *red, Pending &pd,
-                                     const Lev &R, int &rstat, Counts &cnt) {
+                                     const Lev &R, int &rstat, Counts &cnt, const Carry &cr = Carry{},
+                                     unsigned cpx = ~0u) {
   T7_T(t_top);
   bool stop = (FIRST && x1_out) || out7(ls.x2, ls.y2, A.tx, A.ty);
   if (BAND && !stop && (band_bad(B, ls.y2) || (FIRST && band_bad(A, y1)))) {
@@ -353,7 +468,8 @@ __device__ __forceinline__ int pass7(const TrkArgs &a, const Lev &A, const Lev &
     ls.status = kOOB;
     if (JOB) {  // the previous frame's verdict still needs its own pass
       const Pix q = pix_at(R.w, R.h, pd.x2 + fi, pd.y2 + fj);
-      const float rb = interp(q, AOS ? quad_i(R.img, q, (unsigned)R.w * 12u) : quad(R.img, q, (unsigned)R.w * 4u));
+      const float rb =
+          interp(q, AOS && !LZ ? quad_i(R.img, q, (unsigned)R.w * 12u) : quad(R.img, q, (unsigned)R.w * 4u));
       float v[1] = {on ? fabsf(pd.aim - rb) : 0.0f}, S[1];
       ++cnt.passes;
       sums<1, FAST>(red, lane, on, v, S);
@@ -372,7 +488,45 @@ __device__ __forceinline__ int pass7(const TrkArgs &a, const Lev &A, const Lev &
   // a later pass whose corners are the last pass's pixels in every lane (the
   // position moved within its cell): no round trip (wave-uniform test)
   const bool reuse = !FIRST && KLT_T7_REUSE && __ballot(qb.px != ls.bpx) == 0ull;
-  if (reuse) {
+  Pix qa = qb, qr = qb;
+  Quad ai{}, ax{}, ay{}, ri{};
+  if constexpr (LZ == 2) {
+    // image 2's patch (unless the corners are reused), on a first pass image
+    // 1's as well; every global load of the pass is issued before any is used
+    float *pat = red + kRedF;
+    if (FIRST) qa = pix_at(A.w, A.h, x1 + fi, y1 + fj);
+    if (JOB) {
+      qr = pix_at(R.w, R.h, pd.x2 + fi, pd.y2 + fj);
+      ri = quad(R.img, qr, (unsigned)R.w * 4u);
+    }
+    const int X0b = u((int)(ls.x2 - (float)kHw)), Y0b = u((int)(ls.y2 - (float)kHw));
+    const int cxb = (int)(ls.x2 + fi) - X0b, cyb = (int)(ls.y2 + fj) - Y0b;
+    // image 1's corners kept from the previous frame's last pass (wave-uniform test)
+    const bool carry = FIRST && KLT_T7_CARRY && __ballot(qa.px != cpx) == 0ull;
+    if (reuse) {
+      bi = ls.bi;
+      bx = ls.bx;
+      by = ls.by;
+    } else if (!FIRST || carry) {
+      float v[4];
+      patch_load(B.img, B.w, B.h, X0b, Y0b, lane, v);
+      patch_grads(pat, lane, a, B.w, B.h, v, X0b, Y0b, cxb, cyb, bi, bx, by);
+      if (FIRST) ai = cr.i, ax = cr.x, ay = cr.y;
+    } else if (A.il == kLayoutImg) {
+      const int X0a = u((int)(x1 - (float)kHw)), Y0a = u((int)(y1 - (float)kHw));
+      float v[4], va[4];
+      patch_load(B.img, B.w, B.h, X0b, Y0b, lane, v);
+      patch_load(A.img, A.w, A.h, X0a, Y0a, lane, va);
+      patch_grads(pat, lane, a, B.w, B.h, v, X0b, Y0b, cxb, cyb, bi, bx, by);
+      patch_grads(pat, lane, a, A.w, A.h, va, X0a, Y0a, (int)(x1 + fi) - X0a, (int)(y1 + fj) - Y0a, ai, ax, ay);
+    } else {  // a whole previous pyramid: interleaved
+      float v[4];
+      patch_load(B.img, B.w, B.h, X0b, Y0b, lane, v);
+      const Tri t = tri(A.img, qa, (unsigned)A.w * 12u);
+      patch_grads(pat, lane, a, B.w, B.h, v, X0b, Y0b, cxb, cyb, bi, bx, by);
+      ai = t.i, ax = t.x, ay = t.y;
+    }
+  } else if (reuse) {
     bi = ls.bi;
     bx = ls.bx;
     by = ls.by;
@@ -392,9 +546,7 @@ __device__ __forceinline__ int pass7(const TrkArgs &a, const Lev &A, const Lev &
     ls.bx = bx;
     ls.by = by;
   }
-  Pix qa = qb, qr = qb;
-  Quad ai{}, ax{}, ay{}, ri{};
-  if (FIRST) {
+  if (FIRST && LZ != 2) {
     const unsigned rowA = (unsigned)A.w * (AOS ? 12u : 4u);
     qa = pix_at(A.w, A.h, x1 + fi, y1 + fj);
     if constexpr (AOS) {
@@ -408,9 +560,9 @@ __device__ __forceinline__ int pass7(const TrkArgs &a, const Lev &A, const Lev &
       ay = quad(A.gy, qa, rowA);
     }
   }
-  if (JOB) {
+  if (JOB && LZ != 2) {
     qr = pix_at(R.w, R.h, pd.x2 + fi, pd.y2 + fj);
-    ri = AOS ? quad_i(R.img, qr, (unsigned)R.w * 12u) : quad(R.img, qr, (unsigned)R.w * 4u);
+    ri = AOS && !LZ ? quad_i(R.img, qr, (unsigned)R.w * 12u) : quad(R.img, qr, (unsigned)R.w * 4u);
   }
   if (FIRST) {
     ls.aim = interp(qa, ai);
@@ -466,21 +618,31 @@ __device__ __forceinline__ int pass7(const TrkArgs &a, const Lev &A, const Lev &
 // feature the level stops at once and lost_prev is set).  defer: this
 // (finest) level hands its own residue on (pd) instead of taking a pass for
 // it.  residue: the finest level.
-template <bool BAND, bool AOS, bool FAST>
+template <bool BAND, bool AOS, bool FAST, int LZ = 0>
 __device__ int level7(const TrkArgs &a, const Lev &A, const Lev &B, float x1, float y1, float &x2, float &y2,
                       int lane, float fi, float fj, bool on, float *red, bool residue, bool defer, Pending &pd,
-                      bool job, const Lev &R, int &rstat, bool &lost_prev, Counts &cnt) {
+                      bool job, const Lev &R, int &rstat, bool &lost_prev, Counts &cnt, Carry *cr = nullptr,
+                      unsigned cpx = ~0u) {
   const bool x1_out = out7(x1, y1, A.tx, A.ty);
   LevState ls;
   ls.x2 = x2;
   ls.y2 = y2;
-  int r = job ? pass7<BAND, true, true, AOS, FAST>(a, A, B, x1, y1, x1_out, ls, lane, fi, fj, on, red, pd, R, rstat, cnt)
-              : pass7<BAND, true, false, AOS, FAST>(a, A, B, x1, y1, x1_out, ls, lane, fi, fj, on, red, pd, R, rstat,
-                                                    cnt);
+  const Carry none{};
+  const Carry &c0 = LZ == 2 ? *cr : none;
+  int r = job ? pass7<BAND, true, true, AOS, FAST, LZ>(a, A, B, x1, y1, x1_out, ls, lane, fi, fj, on, red, pd, R, rstat,
+                                                       cnt, c0, cpx)
+              : pass7<BAND, true, false, AOS, FAST, LZ>(a, A, B, x1, y1, x1_out, ls, lane, fi, fj, on, red, pd, R, rstat,
+                                                        cnt, c0, cpx);
   while (r == kPassAgain)
-    r = pass7<BAND, false, false, AOS, FAST>(a, A, B, x1, y1, x1_out, ls, lane, fi, fj, on, red, pd, R, rstat, cnt);
+    r = pass7<BAND, false, false, AOS, FAST, LZ>(a, A, B, x1, y1, x1_out, ls, lane, fi, fj, on, red, pd, R, rstat, cnt);
   x2 = ls.x2;
   y2 = ls.y2;
+  if constexpr (LZ == 2 && KLT_T7_CARRY && KLT_T7_REUSE) {  // this frame's image 2 is the next frame's image 1
+    cr->px = ls.bpx;
+    cr->i = ls.bi;
+    cr->x = ls.bx;
+    cr->y = ls.by;
+  }
   if (r == kPassLostPrev) {
     lost_prev = true;
     return kTracked;
@@ -505,7 +667,8 @@ __device__ int level7(const TrkArgs &a, const Lev &A, const Lev &B, float x1, fl
   ++cnt.passes;
   T7_T(t_r0);
   const Pix q = pix_at(B.w, B.h, x2 + fi, y2 + fj);
-  const float rb = interp(q, AOS ? quad_i(B.img, q, (unsigned)B.w * 12u) : quad(B.img, q, (unsigned)B.w * 4u));
+  const float rb =
+      interp(q, AOS && LZ != 2 ? quad_i(B.img, q, (unsigned)B.w * 12u) : quad(B.img, q, (unsigned)B.w * 4u));
   float v[1] = {on ? fabsf(ls.aim - rb) : 0.0f}, S1[1];
   sums<1, FAST>(red, lane, on, v, S1);
   T7_ADD(3, t_r0);
@@ -529,10 +692,17 @@ __device__ int level7(const TrkArgs &a, const Lev &A, const Lev &B, float x1, fl
 // starts with an empty corner-reuse cache (LevState::bpx), so no corners of
 // one direction's image 2 reach the other's or the next frame's; the bounds
 // thresholds (oobx/ooby) depend on the level's size only and serve both.
-template <bool BAND, bool AOS, int NL, bool FAST = false>
-__global__ __launch_bounds__(kBlock) void k_track7(TrkArgs a, TrkFramesArgs b, float *__restrict__ fx,
+// LAZY: level 0 of the bank is the img plane alone (klt_hip_set_lazy_grad);
+// each wave's LDS then holds a gradient patch past its ordered-sum rows.
+// Its two-level instances are held to five waves per SIMD (96 VGPRs; they
+// take 95 and 92, no scratch), so that 5000 features are resident at once; the
+// runtime-depth one (a one-level pyramid) takes 101 without a bound.  The
+// other instances' bound of 1 wave is no constraint.
+template <bool BAND, bool AOS, int NL, bool FAST = false, bool LAZY = false>
+__global__ __launch_bounds__(kBlock, LAZY && NL == 2 ? 5 : LAZY ? 4 : 1) void k_track7(TrkArgs a, TrkFramesArgs b, float *__restrict__ fx,
                                                    float *__restrict__ fy, int *__restrict__ fv, int n) {
-  __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRows * kRow + 4];
+  static_assert(!LAZY || (AOS && !BAND), "lazy gradients: whole-frame interleaved pyramids");
+  __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF + (LAZY ? kPat : 0)];
   constexpr bool FB = false;
   const TrkFbArgs fb{};
 #include "track7_body.h"
@@ -543,8 +713,8 @@ template <bool AOS, int NL>
 __global__ __launch_bounds__(kBlock) void k_track7_fb(TrkArgs a, TrkFramesArgs b, TrkFbArgs fb,
                                                       float *__restrict__ fx, float *__restrict__ fy,
                                                       int *__restrict__ fv, int n) {
-  __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRows * kRow + 4];
-  constexpr bool BAND = false, FAST = false, FB = true;
+  __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
+  constexpr bool BAND = false, FAST = false, FB = true, LAZY = false;
 #include "track7_body.h"
 }
 
@@ -599,6 +769,20 @@ hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const T
       hipLaunchKernelGGL((k_track7_fb<true, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, *fb, x, y, v, n);
     else
       hipLaunchKernelGGL((k_track7_fb<false, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, *fb, x, y, v, n);
+    return hipGetLastError();
+  }
+  if (a.lazy) {  // the runtime sends whole-frame interleaved pyramids here (fast sums: two levels)
+    if (band || !a.aos || (a.fast && !two)) return hipErrorInvalidValue;
+    if (name)
+      *name = a.fast ? "kltdev::k_track7<false, true, 2, true, true>"
+              : two  ? "kltdev::k_track7<false, true, 2, false, true>"
+                     : "kltdev::k_track7<false, true, 0, false, true>";
+    if (a.fast)
+      hipLaunchKernelGGL((k_track7<false, true, 2, true, true>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y, v, n);
+    else if (two)
+      hipLaunchKernelGGL((k_track7<false, true, 2, false, true>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y, v, n);
+    else
+      hipLaunchKernelGGL((k_track7<false, true, 0, false, true>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y, v, n);
     return hipGetLastError();
   }
   // the instance's name as rocprofv3 reports it (bench.py matches PMC summaries on it)

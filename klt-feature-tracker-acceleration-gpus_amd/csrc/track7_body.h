@@ -2,7 +2,7 @@
 // included inside each kernel: the FB-off kernels keep their by-value
 // arguments and compile to what they were before the forward-backward
 // instances existed.  The including kernel provides: the template parameters
-// BAND, AOS, NL, FAST; constexpr bool FB; TrkArgs a; TrkFramesArgs b;
+// BAND, AOS, NL, FAST, LAZY; constexpr bool FB; TrkArgs a; TrkFramesArgs b;
 // TrkFbArgs fb; fx, fy, fv, n; and the LDS array red_all.
   if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -15,7 +15,7 @@
   if (slot >= n) return;  // whole wave; no workgroup barrier in this kernel
   const int f = u(b.perm ? b.perm[slot] : slot);
   float *red = red_all[wave];
-  for (int i = lane; i < kRows * kRow + 4; i += kWave) red[i] = 0.0f;  // pads stay +0
+  for (int i = lane; i < kRedF; i += kWave) red[i] = 0.0f;  // pads stay +0
   wave_lds_sync();
   // lane p < 49: window pixel p; lanes past the window take the last pixel's
   // offsets (valid addresses) and contribute nothing
@@ -29,6 +29,7 @@
   const bool merge = !FB && a.merge_res && nlev >= 2;
   Pending pd;
   Counts cnt;
+  Carry carry;  // lazy-gradient instances: the last level-0 pass's image-2 corners (unused otherwise)
 #ifdef KLT_TRACK_PROF
   const unsigned long long wall0 = wall_clock64();
 #endif
@@ -40,6 +41,10 @@
     if (v >= 0 || job) {
       // one frame of KLTTrackFeatures for this feature (:1348-1437)
       const Lev R = lev_prev(a, b, 0, j);
+      // the corners kept from frame j-1 serve this frame's level 0 only: a frame
+      // that does not reach level 0 leaves nothing for the one after it
+      const unsigned cpx = carry.px;
+      carry.px = ~0u;
       float xl = x, yl = y;
 #pragma unroll
       for (int r = nlev - 1; r >= 0; --r) {  // xloc /= subsampling, nlev times (:1352-1355)
@@ -59,7 +64,12 @@
         const Lev LB = lev_of(a.B[r], (long)j * b.lfs[r], a.oobx[r], a.ooby[r]);
         const bool lj = job && r == nlev - 1;
         T7_T(t_l0);
-        val = level7<BAND, AOS, FAST>(a, LA, LB, xl, yl, xo, yo, lane, fi, fj, on, red, r == 0,
+        if (LAZY && r == 0)
+          val = level7<BAND, AOS, FAST, LAZY ? 2 : 0>(a, LA, LB, xl, yl, xo, yo, lane, fi, fj, on, red, true,
+                                                      merge && j + 1 < b.nframes, pd, lj, R, rstat, lost_prev, cnt,
+                                                      &carry, cpx);
+        else
+          val = level7<BAND, AOS, FAST, LAZY ? 1 : 0>(a, LA, LB, xl, yl, xo, yo, lane, fi, fj, on, red, r == 0,
                            merge && r == 0 && j + 1 < b.nframes, pd, lj, R, rstat, lost_prev, cnt);
         T7_ADD(10, t_l0);
         if (lost_prev) break;
