@@ -288,6 +288,59 @@ int klt_hip_affine_get(klt_hip_ctx *ctx, const int *idx, int m, float *win);
 int klt_hip_track_affine(klt_hip_ctx *ctx, int slot1, int slot2, const klt_hip_track_desc *tdesc,
                          const klt_hip_affine_desc *adesc, float *x, float *y, int *val, float *aff,
                          int *state, int n);
+/* The same check inside the tracker launch of the device-resident calls, off
+   by default.  With it on (adesc != NULL), every tracked frame of
+   klt_hip_track (on_device = 1), klt_hip_track_sequence, klt_hip_track_frames
+   and klt_hip_track_frames_host is followed, in the same launch and before the
+   next frame's translation step, by the reference's record stage
+   (trackFeatures.c:1438-1497) for every feature that step left TRACKED:
+     no window held -- the (ww+2) x (wh+2) img/gradx/grady window of the
+       previous frame's level 0 around the position the frame started from is
+       stored and aff_x / aff_y are set; nothing else changes;
+     window held    -- _am_trackFeatureAffine runs from the stored window into
+       the current frame's level 0.  On failure x = y = aff_x = aff_y = -1, val
+       gets the status and the window is dropped; on success x / y stay the
+       translation result and A is updated.
+   A feature the translation step loses has no window afterwards.
+     dev_aff    device array, 6 floats per feature (aff_x, aff_y, Axx, Ayx,
+                Axy, Ayy), read and written;
+     dev_state  device array, one int per feature.  In: nonzero = the window
+                store holds this feature's window.  Out: 0 no window held, 1 a
+                window held from before the call, 2 a window stored during
+                this call and still held.
+   The caller keeps both valid while the setting is on.  The window store is
+   klt_hip_affine_reserve / _put / _get's: it must be reserved for at least n
+   features of this window size, or the tracking call fails before any launch.
+   Results are those of klt_hip_track_affine frame by frame, bit for bit, and do
+   not depend on the chunk or on the tuning hooks.  Such calls run the generic
+   tracker kernels on full level-0 records (klt_hip_set_lazy_grad does not
+   apply; a kept image-only pyramid is completed first, as for any reader that
+   needs its gradients) and take the residue pass in place
+   (klt_hip_set_track_merge is ignored).  Failing with -1 and a message before
+   any launch while it is on: klt_hip_track with host arrays,
+   klt_hip_track_affine, klt_hip_track_frames_band (and the sharded drivers
+   built on it), KLT_HIP_FAST sums, and any tracking call while the
+   forward-backward check is on.  Argument checks as klt_hip_track_affine's
+   (mode 0..2, window odd and >= 3; else -1, settings unchanged).
+   adesc == NULL turns it off, and so does klt_hip_ctx_reset. */
+int klt_hip_set_frames_affine(klt_hip_ctx *ctx, const klt_hip_affine_desc *adesc, float *dev_aff,
+                              int *dev_state);
+int klt_hip_get_frames_affine(klt_hip_ctx *ctx, int *on);
+/* optional device tables with the setting on, either may be NULL: row f of a
+   klt_hip_track_frames / _host call (row 0 of a klt_hip_track call or
+   klt_hip_track_sequence step) receives, after tracked frame f, every
+   feature's six values (dev_aff_tab, rows 6 * stride floats apart) and state
+   (dev_state_tab, rows stride ints apart), stride >= n; lost features too:
+   their current values and state 0.  Both NULL clears it, and so does
+   klt_hip_ctx_reset.  The caller keeps the memory valid while it is set. */
+int klt_hip_set_affine_table(klt_hip_ctx *ctx, float *dev_aff_tab, int *dev_state_tab, long stride);
+/* for callers with host lists (KLTTrackSequence): copy aff[6n] / state[n] into
+   device arrays the context owns and return them (for
+   klt_hip_set_frames_affine), and copy them back.  Synchronous.  The arrays
+   are also klt_hip_track_affine's scratch: valid until the next such call. */
+int klt_hip_affine_state_put(klt_hip_ctx *ctx, const float *aff, const int *state, int n, float **dev_aff,
+                             int **dev_state);
+int klt_hip_affine_state_get(klt_hip_ctx *ctx, float *aff, int *state, int n);
 /* device-resident sequential tracking, one frame per step: for step k, build
    frame t0+k (frames + (t0+k)*stride) on a second stream into the next of
    three slots (one frame ahead of the tracker), then track the device feature

@@ -710,19 +710,52 @@ static _KLT_FloatImage new_window(int sw, int sh, const float *data)
   return w;
 }
 
-/* KLTTrackFeatures' per-feature loop with the affine consistency check
- * (trackFeatures.c:1343-1497) on the device: klt_hip_track_affine.  The
- * stored windows live in the device store; the features' aff_img images are
+/* The affine consistency check (trackFeatures.c:1343-1497) runs on the device.
+ * The stored windows live in the device store; the features' aff_img images are
  * host mirrors of them (the reference's own representation), written when a
  * window is stored and uploaded again only when a slot holds a window the
  * store does not (a different list, a reallocated store, or a window the
- * caller placed there). */
-static void track_affine(KLT_TrackingContext tc, KLT_FeatureList fl, int slot1, int slot2,
-                         const klt_hip_track_desc *td, float *x, float *y, int *v)
+ * caller placed there).  affine_begin brings the store up to date with the
+ * list and fills aff / state for the device call; affine_end takes the call's
+ * results back into the list.  Both serve one klt_hip_track_affine call
+ * (KLTTrackFeatures) and one batched call with the check inside the tracker
+ * launch (KLTTrackSequence). */
+typedef struct {
+  float *aff;
+  int *state, *idx;
+} affine_io;
+
+static void affine_check_tc(KLT_TrackingContext tc)
+{
+  if (tc->affineConsistencyCheck > 2)
+    KLTError("(KLTTrackFeatures) affineConsistencyCheck=%d: expected -1, 0, 1 or 2", tc->affineConsistencyCheck);
+  if (tc->affineConsistencyCheck >= 0 &&
+      (tc->affine_window_width % 2 != 1 || tc->affine_window_height % 2 != 1 || tc->affine_window_width < 3 ||
+       tc->affine_window_height < 3))
+    KLTError("(KLTTrackFeatures) affine window %d by %d: must be odd and at least 3 (an even one overruns "
+             "the reference's stored window, trackFeatures.c:680-689)",
+             tc->affine_window_width, tc->affine_window_height);
+}
+
+static void affine_desc(KLT_TrackingContext tc, klt_hip_affine_desc *ad)
+{
+  ad->mode = tc->affineConsistencyCheck;
+  ad->window_width = tc->affine_window_width;
+  ad->window_height = tc->affine_window_height;
+  ad->max_iterations = tc->affine_max_iterations;
+  ad->min_determinant = tc->min_determinant;
+  ad->min_displacement = tc->min_displacement;
+  ad->affine_min_displacement = tc->affine_min_displacement;
+  ad->max_residue = tc->affine_max_residue;
+  ad->max_displacement_differ = tc->affine_max_displacement_differ;
+  ad->step_factor = tc->step_factor;
+  ad->lighting_insensitive = tc->lighting_insensitive;
+}
+
+static void affine_begin(KLT_TrackingContext tc, KLT_FeatureList fl, affine_io *io)
 {
   klt_ctx_full *f = FULL(tc);
   klt_hip_ctx *dev = f->dev;
-  klt_hip_affine_desc ad;
   const int n = fl->nFeatures, sw = tc->affine_window_width + 2, sh = tc->affine_window_height + 2;
   const int S = sw * sh;
   float *aff = (float *)malloc(sizeof(float) * 6 * (n + 1));
@@ -767,23 +800,26 @@ static void track_affine(KLT_TrackingContext tc, KLT_FeatureList fl, int slot1, 
     }
     dev_check(tc, klt_hip_affine_put(dev, idx, m, win), "affine window upload");
     free(win);
-    win = NULL;
   }
+  io->aff = aff;
+  io->state = state;
+  io->idx = idx;
+}
 
-  ad.mode = tc->affineConsistencyCheck;
-  ad.window_width = tc->affine_window_width;
-  ad.window_height = tc->affine_window_height;
-  ad.max_iterations = tc->affine_max_iterations;
-  ad.min_determinant = tc->min_determinant;
-  ad.min_displacement = tc->min_displacement;
-  ad.affine_min_displacement = tc->affine_min_displacement;
-  ad.max_residue = tc->affine_max_residue;
-  ad.max_displacement_differ = tc->affine_max_displacement_differ;
-  ad.step_factor = tc->step_factor;
-  ad.lighting_insensitive = tc->lighting_insensitive;
-  dev_check(tc, klt_hip_track_affine(dev, slot1, slot2, td, &ad, x, y, v, aff, state, n), "feature tracking");
+/* x, y, v: the list after the call; io->aff / io->state: as the device left them */
+static void affine_end(KLT_TrackingContext tc, KLT_FeatureList fl, const float *x, const float *y, const int *v,
+                       affine_io *io)
+{
+  klt_ctx_full *f = FULL(tc);
+  klt_hip_ctx *dev = f->dev;
+  const int n = fl->nFeatures, sw = tc->affine_window_width + 2, sh = tc->affine_window_height + 2;
+  const int S = sw * sh;
+  const float *aff = io->aff;
+  const int *state = io->state;
+  int *idx = io->idx;
+  float *win;
+  int k, m = 0;
 
-  m = 0;
   for (k = 0; k < n; k++) {
     KLT_Feature ft = fl->feature[k];
     if (ft->val < 0) continue; /* untouched, like the reference (:1346) */
@@ -817,9 +853,25 @@ static void track_affine(KLT_TrackingContext tc, KLT_FeatureList fl, int slot1, 
     }
     free(win);
   }
-  free(aff);
-  free(state);
-  free(idx);
+  free(io->aff);
+  free(io->state);
+  free(io->idx);
+  io->aff = NULL;
+  io->state = io->idx = NULL;
+}
+
+/* KLTTrackFeatures' per-feature loop with the check: klt_hip_track_affine */
+static void track_affine(KLT_TrackingContext tc, KLT_FeatureList fl, int slot1, int slot2,
+                         const klt_hip_track_desc *td, float *x, float *y, int *v)
+{
+  klt_hip_affine_desc ad;
+  affine_io io;
+
+  affine_begin(tc, fl, &io);
+  affine_desc(tc, &ad);
+  dev_check(tc, klt_hip_track_affine(FULL(tc)->dev, slot1, slot2, td, &ad, x, y, v, io.aff, io.state, fl->nFeatures),
+            "feature tracking");
+  affine_end(tc, fl, x, y, v, &io);
 }
 
 /* KLTTrackFeatures (trackFeatures.c:1234-1529) */
@@ -840,14 +892,7 @@ EXPORT void KLTTrackFeatures(KLT_TrackingContext tc, KLT_PixelType *img1, KLT_Pi
     fflush(stderr);
   }
   window_fix(tc, NULL);
-  if (tc->affineConsistencyCheck > 2)
-    KLTError("(KLTTrackFeatures) affineConsistencyCheck=%d: expected -1, 0, 1 or 2", tc->affineConsistencyCheck);
-  if (tc->affineConsistencyCheck >= 0 &&
-      (tc->affine_window_width % 2 != 1 || tc->affine_window_height % 2 != 1 || tc->affine_window_width < 3 ||
-       tc->affine_window_height < 3))
-    KLTError("(KLTTrackFeatures) affine window %d by %d: must be odd and at least 3 (an even one overruns "
-             "the reference's stored window, trackFeatures.c:680-689)",
-             tc->affine_window_width, tc->affine_window_height);
+  affine_check_tc(tc);
   dev = device_of(tc);
   apply_fb(tc, "KLTTrackFeatures");
 
@@ -977,12 +1022,15 @@ EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int
   taps_state st, after1;
   store_rows_ctx sr;
   int k, i, seq_start, steady, seed_first, n = fl->nFeatures, T = nframes - 1;
+  const int affine = tc->affineConsistencyCheck >= 0;
+  affine_io aio;
   const unsigned char *const *src;
   float *hx, *hy;
   int *hv;
 
   if (nframes < 2) return;
   window_fix(tc, NULL);
+  affine_check_tc(tc);
   if (ft && (ft_col < 0 || ft_col + T > ft->nFrames))
     KLTError("(KLTStoreFeatures) Frame number %d is not between 0 and %d", ft_col < 0 ? ft_col : ft_col + T - 1,
              ft->nFrames - 1);
@@ -1008,8 +1056,7 @@ EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int
   if (!tc->sequentialMode) pyr_desc_in(&st, tc, ncols, nrows, tc->nPyramidLevels, 1, &e1);
   pyr_desc_in(&st, tc, ncols, nrows, tc->nPyramidLevels, 1, &e2);
   steady = taps_state_eq(&st, &after1) && !memcmp(&e2, &d2, sizeof d2) &&
-           (tc->sequentialMode || !memcmp(&e1, &d2, sizeof d2)) && !tc->writeInternalImages &&
-           tc->affineConsistencyCheck < 0; /* the affine stage runs per KLTTrackFeatures call */
+           (tc->sequentialMode || !memcmp(&e1, &d2, sizeof d2)) && !tc->writeInternalImages;
   if (!steady) {
     for (i = 1; i < nframes; i++) {
       KLTTrackFeatures(tc, frames[i - 1], frames[i], ncols, nrows, fl);
@@ -1051,16 +1098,35 @@ EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int
   }
   sr.ft = ft;
   sr.col = ft_col;
-  dev_check(tc, klt_hip_track_frames_host(dev, &d2, &td, src, seed_first ? nframes : nframes - 1, seed_first,
-                                          SEQ_CHUNK, hx, hy, hv, n, ft ? store_rows : NULL, &sr),
-            "sequence tracking");
-  for (k = 0; k < n; k++) {
-    KLT_Feature ftr = fl->feature[k];
-    if (ftr->val < 0) continue; /* untouched, like the reference (:1346) */
-    ftr->x = hx[k];
-    ftr->y = hy[k];
-    ftr->val = hv[k];
-    if (hv[k] != KLT_TRACKED) drop_affine(ftr);
+  if (affine) {
+    /* the check runs inside the tracker launch (klt_hip_set_frames_affine) on
+       device copies of the list's affine state; the list ends as the per-call
+       loop would leave it */
+    klt_hip_affine_desc ad;
+    float *d_aff = NULL;
+    int *d_state = NULL, rc;
+    affine_begin(tc, fl, &aio);
+    affine_desc(tc, &ad);
+    dev_check(tc, klt_hip_affine_state_put(dev, aio.aff, aio.state, n, &d_aff, &d_state), "affine state upload");
+    dev_check(tc, klt_hip_set_frames_affine(dev, &ad, d_aff, d_state), "affine check");
+    rc = klt_hip_track_frames_host(dev, &d2, &td, src, seed_first ? nframes : nframes - 1, seed_first, SEQ_CHUNK, hx,
+                                   hy, hv, n, ft ? store_rows : NULL, &sr);
+    klt_hip_set_frames_affine(dev, NULL, NULL, NULL); /* off again, whatever the call returned */
+    dev_check(tc, rc, "sequence tracking");
+    dev_check(tc, klt_hip_affine_state_get(dev, aio.aff, aio.state, n), "affine state download");
+    affine_end(tc, fl, hx, hy, hv, &aio);
+  } else {
+    dev_check(tc, klt_hip_track_frames_host(dev, &d2, &td, src, seed_first ? nframes : nframes - 1, seed_first,
+                                            SEQ_CHUNK, hx, hy, hv, n, ft ? store_rows : NULL, &sr),
+              "sequence tracking");
+    for (k = 0; k < n; k++) {
+      KLT_Feature ftr = fl->feature[k];
+      if (ftr->val < 0) continue; /* untouched, like the reference (:1346) */
+      ftr->x = hx[k];
+      ftr->y = hy[k];
+      ftr->val = hv[k];
+      if (hv[k] != KLT_TRACKED) drop_affine(ftr);
+    }
   }
   free(hx);
   free(hy);

@@ -7,7 +7,9 @@
 //   track7.hip    k_track7 (the Newton loop of the default configuration)
 //                 both with forward-backward instances (k_*_fb); the kernels'
 //                 bodies are track_body.h / track7_body.h
-//   affine.hip    k_affine (the affine consistency check)
+//   affine.hip    k_affine (the affine consistency check, one frame pair per
+//                 launch); its per-feature stage is affine_dev.h, which
+//                 track.hip's k_track_frames_g_aff runs inside the batched launch
 //   runtime.hip   host side: device contexts, slots and banks, pipelines,
 //                 the klt_hip_* C ABI (include/klt_hip.h)
 //
@@ -159,6 +161,11 @@ constexpr int kProfN = 12;       // instrumented build: counters per wave
 // ---------------------------------------------------------------------------
 // affine consistency check arguments (affine.hip)
 // ---------------------------------------------------------------------------
+struct AffParams {
+  int mode, ww, wh, max_it, li;
+  float min_det, th, th_aff, max_res, mdd, step;
+};
+
 struct AffArgs {
   const float *ai, *agx, *agy;  // image 1, level 0
   const float *bi, *bgx, *bgy;  // image 2, level 0
@@ -170,9 +177,30 @@ struct AffArgs {
   float *aff;            // 6 per feature: aff_x, aff_y, Axx, Ayx, Axy, Ayy
   int *state;            // in: 1 window stored, 0 none; out: 0, 1, 2 = stored by this call
   float *store;          // 3*S floats per feature
-  int n, mode, ww, wh, max_it, li;
-  float min_det, th, th_aff, max_res, mdd, step;
+  int n;
+  AffParams p;
 };
+
+// the check inside the batched tracker launch (klt_hip_set_frames_affine): the
+// affine instances take this beside TrkFramesArgs, so the others keep their
+// argument layout
+struct TrkAffArgs {
+  AffParams p;
+  float *aff;    // 6 per feature (in/out)
+  int *state;    // in: nonzero = window held; out: 0, 1 held from before, 2 stored by this call
+  float *store;  // 3*S floats per feature
+  int fresh;     // 1: the call's first launch (a held window is state 1); 0: a later one (2 stays 2)
+  int lds_wave;  // floats of dynamic LDS per wave: the staging and the solve's block
+  float *tab_aff;  // optional tables: row j receives the values / states after frame j
+  int *tab_state;
+  long stride;     // features per table row (the affine row is 6 * stride floats)
+};
+// pixels per ordered-sum chunk of the affine stage inside the tracker launch
+// ("The affine check in the batched launch")
+#ifndef KLT_AFF_CH
+#define KLT_AFF_CH 64
+#endif
+constexpr int kAffChunk = KLT_AFF_CH;
 
 // ---------------------------------------------------------------------------
 // launchers
@@ -215,9 +243,12 @@ hipError_t launch_selftest_div(const float *a, const float *b, float *out, int n
 // the tracker: one wave per feature; patch/win7 select the lane-patch gather
 // and the compiled-in 7x7 window, npx the pixels-per-lane instance
 // fb != nullptr: the forward-backward instances (exact sums, no band checks)
+// af != nullptr: the affine-check instances (the same; not together with fb)
 hipError_t launch_track_frames(hipStream_t st, bool exact, bool li, bool patch, bool win7, int npx,
                                const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y, int *v, int n,
-                               const TrkFbArgs *fb = nullptr);
+                               const TrkFbArgs *fb = nullptr, const TrkAffArgs *af = nullptr);
+// dynamic LDS bytes a workgroup of the affine instances needs for `mode`
+size_t track_affine_lds_bytes(int mode);
 // track7.hip: the default configuration (7x7 window, exact sums, no gain/bias,
 // one wave per feature) with the latency-lean pass; band: escape checks
 hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y,

@@ -322,6 +322,18 @@ struct klt_hip_ctx {
   float fb_dist = 0.0f;
   float *fb_tab = nullptr;
   long fb_stride = 0;
+  // affine check inside the tracker launch (klt_hip_set_frames_affine): the
+  // caller's device arrays, the optional tables (klt_hip_set_affine_table);
+  // aff_fresh: the next tracker launch is the first of its API call (windows
+  // held on entry are state 1), aff_depth: nesting of the entry points
+  int aff_on = 0;
+  AffParams aff_p{};
+  float *aff_dev = nullptr;
+  int *aff_state_dev = nullptr;
+  float *aff_tab = nullptr;
+  int *aff_stab = nullptr;
+  long aff_tab_stride = 0;
+  int aff_fresh = 1, aff_depth = 0;
   // band calls: 1 = the next chunk's frames are ready when the call is made
   // (not written by work still queued on the tracking stream), so its
   // build-ahead waits for its bank and for this chunk's processing order
@@ -878,12 +890,46 @@ int fb_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const cha
   return 0;
 }
 
+// The affine check inside the launch (klt_hip_set_frames_affine) has instances
+// for exact sums on whole-frame pyramids, without the forward-backward check;
+// its window store must hold n features' windows of this size and its tables
+// n features per row: anything else fails before a launch.
+int aff_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, int n, const char *who) {
+  if (!c->aff_on) return 0;
+  if (band) return fail(c, "%s: the affine check does not cover band calls (klt_hip_set_frames_affine)", who);
+  if (d->reduction != KLT_HIP_EXACT)
+    return fail(c, "%s: the affine check needs KLT_HIP_EXACT sums (klt_hip_set_frames_affine)", who);
+  if (c->fb_on)
+    return fail(c, "%s: the forward-backward check does not combine with the affine check "
+                "(klt_hip_set_fb, klt_hip_set_frames_affine)", who);
+  const int S = (c->aff_p.ww + 2) * (c->aff_p.wh + 2);
+  if (n > 0 && (!c->d_aff_store || c->aff_S != S || c->aff_store_cap < (size_t)n * 3 * S))
+    return fail(c, "%s: affine window store not reserved for %d features of %dx%d (klt_hip_affine_reserve)", who, n,
+                c->aff_p.ww, c->aff_p.wh);
+  if ((c->aff_tab || c->aff_stab) && c->aff_tab_stride < n)
+    return fail(c, "%s: affine table stride %ld < n %d", who, c->aff_tab_stride, n);
+  return 0;
+}
+
+// an entry point that tracks: the first tracker launch inside the outermost
+// one is the call's first (TrkAffArgs::fresh)
+struct AffCall {
+  klt_hip_ctx *c;
+  explicit AffCall(klt_hip_ctx *ctx) : c(ctx) {
+    if (c && c->aff_depth++ == 0) c->aff_fresh = 1;
+  }
+  ~AffCall() {
+    if (c) --c->aff_depth;
+  }
+};
+
 // ordered: the caller ran order_features into b already; fb_row: the
-// forward-backward table row of this launch's first frame
+// forward-backward / affine table row of this launch's first frame
 int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc *d, const TrkArgs &a,
                         const TrkFramesArgs &b, float *x, float *y, int *v, int n, const float *own = nullptr,
                         bool ordered = false, long fb_row = 0) {
   if (fb_refused(c, d, own != nullptr || a.escape != nullptr, "track")) return -1;
+  if (aff_refused(c, d, own != nullptr || a.escape != nullptr, n, "track")) return -1;
   if (c->fb_on && c->fb_tab && c->fb_stride < n)
     return fail(c, "track: forward-backward table stride %ld < n %d", c->fb_stride, n);
   TimedScope ts(c, T_TRACK, st, b.nframes);
@@ -907,7 +953,9 @@ int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc
   // covers interleaved two-level pyramids; other fast cases take the generic
   // kernel's tree sums
   const bool ilA = a.A[0].il != 0, ilB = a.B[0].il != 0;
-  const bool t7 = t7_tracks(c, d) && (exact || (ilA && ilB && a.nlev == 2));
+  // the affine check runs in the generic family only (a 15x15 affine window
+  // costs far more than the lean kernel saves on the 7x7 translation step)
+  const bool t7 = !c->aff_on && t7_tracks(c, d) && (exact || (ilA && ilB && a.nlev == 2));
   if (t7 && ilA && ilB) {
     aa.aos = 1;
     aa.fast = exact ? 0 : 1;
@@ -936,8 +984,23 @@ int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc
   const TrkFbArgs *fbp = c->fb_on ? &fb : nullptr;
   if (t7)
     return launched(c, "k_track7", launch_track7(st, aa.escape != nullptr, aa, b2, x, y, v, n, &c->track_kernel, fbp));
-  c->track_kernel = fbp ? "kltdev::k_track_frames_g_fb" : "kltdev::k_track_frames_g";
-  return launched(c, "k_track_frames", launch_track_frames(st, exact, li, patch, win7, npx, aa, b2, x, y, v, n, fbp));
+  TrkAffArgs af{};
+  if (c->aff_on) {
+    af.p = c->aff_p;
+    af.aff = c->aff_dev;
+    af.state = c->aff_state_dev;
+    af.store = c->d_aff_store;
+    af.fresh = c->aff_fresh;
+    af.lds_wave = (int)(track_affine_lds_bytes(af.p.mode) / sizeof(float) / (kBlock / kWave));
+    af.stride = c->aff_tab_stride;
+    af.tab_aff = c->aff_tab ? c->aff_tab + 6 * fb_row * af.stride : nullptr;
+    af.tab_state = c->aff_stab ? c->aff_stab + fb_row * af.stride : nullptr;
+    c->aff_fresh = 0;
+  }
+  const TrkAffArgs *afp = c->aff_on ? &af : nullptr;
+  c->track_kernel = afp ? "kltdev::k_track_frames_g_aff" : fbp ? "kltdev::k_track_frames_g_fb" : "kltdev::k_track_frames_g";
+  return launched(c, "k_track_frames",
+                  launch_track_frames(st, exact, li, patch, win7, npx, aa, b2, x, y, v, n, fbp, afp));
 }
 
 // The three banks live in one device arena per context: for each bank, level
@@ -1446,6 +1509,14 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->fb_dist = 0.0f;
   c->fb_tab = nullptr;
   c->fb_stride = 0;
+  c->aff_on = 0;
+  c->aff_dev = nullptr;
+  c->aff_state_dev = nullptr;
+  c->aff_tab = nullptr;
+  c->aff_stab = nullptr;
+  c->aff_tab_stride = 0;
+  c->aff_fresh = 1;
+  c->aff_depth = 0;
   c->serial_frames = 1;
   c->ahead_ready = 0;
   c->prof = nullptr;
@@ -1784,6 +1855,89 @@ KLT_API int klt_hip_set_fb_table(klt_hip_ctx *c, float *dev_err, long stride) {
   return 0;
 }
 
+// klt_hip_track_affine's and klt_hip_set_frames_affine's argument checks
+static int affine_desc_check(klt_hip_ctx *c, const klt_hip_affine_desc *ad, const char *who) {
+  if (ad->mode < 0 || ad->mode > 2) return fail(c, "%s: mode %d (0, 1 or 2)", who, ad->mode);
+  if (ad->window_width < 3 || ad->window_height < 3 || ad->window_width % 2 == 0 || ad->window_height % 2 == 0)
+    return fail(c, "%s: affine window %dx%d must be odd and >= 3", who, ad->window_width, ad->window_height);
+  return 0;
+}
+
+static AffParams affine_params(const klt_hip_affine_desc *ad) {
+  AffParams p;
+  p.mode = ad->mode;
+  p.ww = ad->window_width;
+  p.wh = ad->window_height;
+  p.max_it = ad->max_iterations;
+  p.li = ad->lighting_insensitive;
+  p.min_det = ad->min_determinant;
+  p.th = ad->min_displacement;
+  p.th_aff = ad->affine_min_displacement;
+  p.max_res = ad->max_residue;
+  p.mdd = ad->max_displacement_differ;
+  p.step = ad->step_factor;
+  return p;
+}
+
+KLT_API int klt_hip_set_frames_affine(klt_hip_ctx *c, const klt_hip_affine_desc *ad, float *dev_aff,
+                                      int *dev_state) {
+  if (!c) return fail(c, "set_frames_affine: null context");
+  if (ad) {
+    if (!dev_aff || !dev_state) return fail(c, "set_frames_affine: null device array");
+    if (affine_desc_check(c, ad, "set_frames_affine")) return -1;
+    c->aff_p = affine_params(ad);
+  }
+  c->aff_on = ad ? 1 : 0;
+  c->aff_dev = ad ? dev_aff : nullptr;
+  c->aff_state_dev = ad ? dev_state : nullptr;
+  return 0;
+}
+
+KLT_API int klt_hip_get_frames_affine(klt_hip_ctx *c, int *on) {
+  if (!c) return fail(c, "get_frames_affine: null context");
+  if (on) *on = c->aff_on;
+  return 0;
+}
+
+KLT_API int klt_hip_set_affine_table(klt_hip_ctx *c, float *dev_aff_tab, int *dev_state_tab, long stride) {
+  if (!c) return fail(c, "set_affine_table: null context");
+  if ((dev_aff_tab || dev_state_tab) && stride < 1) return fail(c, "set_affine_table: stride %ld < 1", stride);
+  c->aff_tab = dev_aff_tab;
+  c->aff_stab = dev_state_tab;
+  c->aff_tab_stride = dev_aff_tab || dev_state_tab ? stride : 0;
+  return 0;
+}
+
+KLT_API int klt_hip_affine_state_put(klt_hip_ctx *c, const float *aff, const int *state, int n, float **dev_aff,
+                                     int **dev_state) {
+  if (!c || !dev_aff || !dev_state || n < 0 || (n > 0 && (!aff || !state)))
+    return fail(c, "affine_state_put: bad argument");
+  if (use_device(c)) return -1;
+  if (grow(c, &c->d_aff, &c->aff_cap, (size_t)(n ? n : 1) * 6) ||
+      grow(c, &c->d_astate, &c->astate_cap, (size_t)(n ? n : 1)))
+    return -1;
+  if (n > 0) {
+    HIPCHK(c, hipMemcpyAsync(c->d_aff, aff, sizeof(float) * n * 6, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_astate, state, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's arrays are pageable: read by now
+  }
+  *dev_aff = c->d_aff;
+  *dev_state = c->d_astate;
+  return 0;
+}
+
+KLT_API int klt_hip_affine_state_get(klt_hip_ctx *c, float *aff, int *state, int n) {
+  if (!c || n < 0 || (n > 0 && (!aff || !state))) return fail(c, "affine_state_get: bad argument");
+  if (n == 0) return 0;
+  if (!c->d_aff || !c->d_astate || c->aff_cap < (size_t)n * 6 || c->astate_cap < (size_t)n)
+    return fail(c, "affine_state_get: no arrays of %d features (klt_hip_affine_state_put)", n);
+  if (use_device(c)) return -1;
+  HIPCHK(c, hipMemcpyAsync(aff, c->d_aff, sizeof(float) * n * 6, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(state, c->d_astate, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 KLT_API int klt_hip_set_track_count(klt_hip_ctx *c, int on) {
   if (!c) return fail(c, "set_track_count: null context");
   if (use_device(c)) return -1;
@@ -1931,6 +2085,11 @@ KLT_API int klt_hip_track(klt_hip_ctx *c, int s1, int s2, const klt_hip_track_de
     if (A.lv[l].w != B.lv[l].w || A.lv[l].h != B.lv[l].h) return fail(c, "track: slot size mismatch");
   if (check_window(c, d)) return -1;
   if (fb_refused(c, d, false, "track")) return -1;
+  if (c->aff_on && !on_device)
+    return fail(c, "track: the affine check inside the launch takes device arrays (on_device = 1; "
+                "klt_hip_set_frames_affine)");
+  if (aff_refused(c, d, false, n, "track")) return -1;
+  AffCall aff_call(c);
   const int npx = d->window_width * d->window_height;
   if (n <= 0) return 0;
   if (use_device(c)) return -1;
@@ -2038,12 +2197,12 @@ KLT_API int klt_hip_track_affine(klt_hip_ctx *c, int s1, int s2, const klt_hip_t
                                  int *state, int n) {
   if (!c || !d || !ad || (n > 0 && (!x || !y || !val || !aff || !state)))
     return fail(c, "track_affine: null argument");
-  if (ad->mode < 0 || ad->mode > 2) return fail(c, "track_affine: mode %d (0, 1 or 2)", ad->mode);
-  if (ad->window_width < 3 || ad->window_height < 3 || ad->window_width % 2 == 0 || ad->window_height % 2 == 0)
-    return fail(c, "track_affine: affine window %dx%d must be odd and >= 3", ad->window_width,
-                ad->window_height);
+  if (affine_desc_check(c, ad, "track_affine")) return -1;
   if (c->fb_on)
     return fail(c, "track_affine: the forward-backward check does not combine with the affine check (klt_hip_set_fb)");
+  if (c->aff_on)
+    return fail(c, "track_affine: the affine check is set to run inside the tracker launch "
+                "(klt_hip_set_frames_affine); turn that off for per-call checks");
   if (n <= 0) return 0;
   if (s1 < 0 || s1 >= KLT_HIP_MAX_SLOTS || s2 < 0 || s2 >= KLT_HIP_MAX_SLOTS)
     return fail(c, "track_affine: bad slot");
@@ -2096,17 +2255,7 @@ KLT_API int klt_hip_track_affine(klt_hip_ctx *c, int s1, int s2, const klt_hip_t
   a.state = c->d_astate;
   a.store = c->d_aff_store;
   a.n = n;
-  a.mode = ad->mode;
-  a.ww = ad->window_width;
-  a.wh = ad->window_height;
-  a.max_it = ad->max_iterations;
-  a.li = ad->lighting_insensitive;
-  a.min_det = ad->min_determinant;
-  a.th = ad->min_displacement;
-  a.th_aff = ad->affine_min_displacement;
-  a.max_res = ad->max_residue;
-  a.mdd = ad->max_displacement_differ;
-  a.step = ad->step_factor;
+  a.p = affine_params(ad);
   if (launched(c, "k_affine", launch_affine(c->stream, a))) return -1;
   HIPCHK(c, hipMemcpyAsync(x, c->d_fx, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(y, c->d_fy, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
@@ -2126,6 +2275,8 @@ KLT_API int klt_hip_track_sequence(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, c
   if (!c || !pd || !td || !frames || !cur_slot) return fail(c, "track_sequence: null argument");
   if (*cur_slot < 0 || *cur_slot > 2) return fail(c, "track_sequence: cur_slot must be 0, 1 or 2");
   if (nsteps <= 0) return 0;
+  if (fb_refused(c, td, false, "track_sequence") || aff_refused(c, td, false, n, "track_sequence")) return -1;
+  AffCall aff_call(c);
   if (use_device(c)) return -1;
   if (!c->pstream) {
     HIPCHK(c, make_pstream(c));
@@ -2334,6 +2485,7 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
   if (pitch < pd->ncols) return fail(c, "track_frames: pitch %ld < ncols %d", pitch, pd->ncols);
   if (check_window(c, td)) return -1;
   if (fb_refused(c, td, band != nullptr, band ? "track_frames_band" : "track_frames")) return -1;
+  if (aff_refused(c, td, band != nullptr, n, band ? "track_frames_band" : "track_frames")) return -1;
   if (c->fb_on && c->fb_tab && c->fb_stride < n)
     return fail(c, "track_frames: forward-backward table stride %ld < n %d", c->fb_stride, n);
   {
@@ -2354,7 +2506,7 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
   // the forward-backward check, from a previous pyramid that is interleaved
   // or image-only itself.  Any other call first makes an image-only previous
   // pyramid whole.
-  const bool lazy = c->lazy_grad && fz && t7_tracks(c, td) && !band && !c->fb_on &&
+  const bool lazy = c->lazy_grad && fz && t7_tracks(c, td) && !band && !c->fb_on && !c->aff_on &&
                     (td->reduction == KLT_HIP_EXACT || pd->nlevels == 2) && prev_level(c, 0).il != kLayoutPlanes;
   if (!lazy && prev_full(c)) return -1;
   if (!c->pstream) {
@@ -2566,6 +2718,7 @@ KLT_API int klt_hip_track_frames(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, con
                                  const unsigned char *frames, long pitch, long stride, int nframes, int chunk,
                                  float *x, float *y, int *val, int n, float *tab_x, float *tab_y, int *tab_val,
                                  long tab_stride) {
+  AffCall aff_call(c);
   return track_frames_impl(c, pd, td, frames, pitch, stride, nframes, chunk, x, y, val, n, tab_x, tab_y, tab_val,
                            tab_stride, nullptr);
 }
@@ -2635,6 +2788,8 @@ KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
   if (!c || !pd || !td || (nframes > 0 && !frames)) return fail(c, "track_frames_host: null argument");
   if (chunk < 1 || nframes < 0 || n < 0) return fail(c, "track_frames_host: bad nframes/chunk/n");
   if (fb_refused(c, td, false, "track_frames_host")) return -1;
+  if (aff_refused(c, td, false, n, "track_frames_host")) return -1;
+  AffCall aff_call(c);
   if (n > 0 && (!x || !y || !val)) return fail(c, "track_frames_host: null feature arrays");
   for (int f = 0; f < nframes; ++f)
     if (!frames[f]) return fail(c, "track_frames_host: frame %d is NULL", f);

@@ -11,11 +11,15 @@
 
 #include <math.h>
 
+#include "affine_dev.h"
 #include "klt_dev.h"
 #include "klt_interp.h"
 
 #ifndef KLT_SUM_BATCH
 #define KLT_SUM_BATCH 4  // 16-byte LDS reads in flight per ordered-sum batch
+#endif
+#ifndef KLT_AFF_WAVES
+#define KLT_AFF_WAVES 1  // the same floor for the affine-check instances with one pixel per lane
 #endif
 #ifndef KLT_TRACK_WAVES
 #define KLT_TRACK_WAVES 1  // amdgpu_waves_per_eu floor for the tracker (1: compiler's choice)
@@ -761,8 +765,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KLT_TRAC
                                                            float *__restrict__ fy, int *__restrict__ fv, int n) {
   constexpr int LG = kWave / G;
   __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][6 * G * (LG * PPL + 4) + 16];
-  constexpr bool FB = false;
+  constexpr bool FB = false, AFF = false;
   const TrkFbArgs fb{};
+  const TrkAffArgs af{};
+  float *const aff_dyn = nullptr;
 #include "track_body.h"
 }
 
@@ -772,7 +778,27 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KLT_TRAC
     int n) {
   constexpr int LG = kWave / G;
   __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][6 * G * (LG * PPL + 4) + 16];
-  constexpr bool EXACT = true, BAND = false, FB = true;
+  constexpr bool EXACT = true, BAND = false, FB = true, AFF = false;
+  const TrkAffArgs af{};
+  float *const aff_dyn = nullptr;
+#include "track_body.h"
+}
+
+// AFF: the affine-check instances (klt_hip_set_frames_affine).  A feature
+// tracked in frame j goes through the reference's record stage
+// (affine_dev.h) before frame j+1: its window of the previous image is stored,
+// or it is re-tracked from the stored window and rejected when that fails.
+// Exact sums, whole-frame pyramids, level 0 as planes, the residue in place.
+// The stage's ordered-sum staging is dynamic LDS sized for the mode.
+template <int G, int PPL, bool PATCH, int WIN, bool LI>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPL == 1 ? KLT_AFF_WAVES : 1))) void k_track_frames_g_aff(
+    TrkArgs a, TrkFramesArgs b, TrkAffArgs af, float *__restrict__ fx, float *__restrict__ fy, int *__restrict__ fv,
+    int n) {
+  constexpr int LG = kWave / G;
+  __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][6 * G * (LG * PPL + 4) + 16];
+  extern __shared__ __attribute__((aligned(16))) float aff_dyn[];
+  constexpr bool EXACT = true, BAND = false, FB = false, AFF = true;
+  const TrkFbArgs fb{};
 #include "track_body.h"
 }
 
@@ -928,11 +954,47 @@ void launch_sel_fb(bool patch, bool win7, int npx, hipStream_t st, const TrkArgs
   else launch_g_fb<1, 16, false, 0, LI>(st, a, b, fb, x, y, v, n);
 }
 
+template <int G, int PPL, bool PATCH, int WIN, bool LI>
+void launch_g_aff(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkAffArgs &af, float *x, float *y,
+                  int *v, int n) {
+  const int per = (kBlock / kWave) * G;
+  const int nb = (n + per - 1) / per;
+  const int grid = b.xcd_per > 0 ? 8 * b.xcd_per : nb;
+  const size_t lds = sizeof(float) * (kBlock / kWave) * (size_t)af.lds_wave;
+  if (lds > (48u << 10))  // a larger KLT_AFF_CH: past the default dynamic allowance
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_track_frames_g_aff<G, PPL, PATCH, WIN, LI>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((k_track_frames_g_aff<G, PPL, PATCH, WIN, LI>), dim3(grid), dim3(kBlock), lds, st, a, b, af, x, y,
+                     v, n);
+}
+
+// launch_sel's choice of instance, for the affine-check kernels
+template <bool LI>
+void launch_sel_aff(bool patch, bool win7, int npx, hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b,
+                    const TrkAffArgs &af, float *x, float *y, int *v, int n) {
+  if (patch && win7) launch_g_aff<1, 1, true, 7, LI>(st, a, b, af, x, y, v, n);
+  else if (patch) launch_g_aff<1, 1, true, 0, LI>(st, a, b, af, x, y, v, n);
+  else if (win7) launch_g_aff<1, 1, false, 7, LI>(st, a, b, af, x, y, v, n);
+  else if (npx <= kWave) launch_g_aff<1, 1, false, 0, LI>(st, a, b, af, x, y, v, n);
+  else if (npx <= 4 * kWave) launch_g_aff<1, 4, false, 0, LI>(st, a, b, af, x, y, v, n);
+  else launch_g_aff<1, 16, false, 0, LI>(st, a, b, af, x, y, v, n);
+}
+
 }  // namespace
+
+size_t track_affine_lds_bytes(int mode) {
+  return sizeof(float) * (kBlock / kWave) * (size_t)(aff::sums_of(mode) * kAffChunk + aff::SOLVE);
+}
 
 hipError_t launch_track_frames(hipStream_t st, bool exact, bool li, bool patch, bool win7, int npx,
                                const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y, int *v, int n,
-                               const TrkFbArgs *fb) {
+                               const TrkFbArgs *fb, const TrkAffArgs *af) {
+  if (af) {  // the runtime refuses band calls, fast sums and the forward-backward check with it on
+    if (!exact || a.escape || fb) return hipErrorInvalidValue;
+    if (li) launch_sel_aff<true>(patch, win7, npx, st, a, b, *af, x, y, v, n);
+    else launch_sel_aff<false>(patch, win7, npx, st, a, b, *af, x, y, v, n);
+    return hipGetLastError();
+  }
   if (fb) {  // the runtime refuses band calls and fast sums with the check on
     if (!exact || a.escape) return hipErrorInvalidValue;
     if (li) launch_sel_fb<true>(patch, win7, npx, st, a, b, *fb, x, y, v, n);

@@ -1,10 +1,10 @@
-// track_body.h -- the body shared by k_track_frames_g and k_track_frames_g_fb
-// (track.hip), included inside each kernel: the FB-off kernels keep their
-// by-value arguments and compile to what they were before the
-// forward-backward instances existed.  The including kernel provides: the
-// template parameters G, PPL, PATCH, WIN, EXACT, LI, BAND; constexpr bool FB;
-// TrkArgs a; TrkFramesArgs b; TrkFbArgs fb; fx, fy, fv, n; and the LDS array
-// red_all.
+// track_body.h -- the body shared by k_track_frames_g, k_track_frames_g_fb and
+// k_track_frames_g_aff (track.hip), included inside each kernel: the plain
+// kernels keep their by-value arguments and compile to what they were before
+// the forward-backward and affine instances existed.  The including kernel
+// provides: the template parameters G, PPL, PATCH, WIN, EXACT, LI, BAND;
+// constexpr bool FB, AFF; TrkArgs a; TrkFramesArgs b; TrkFbArgs fb; TrkAffArgs
+// af; fx, fy, fv, n; the LDS array red_all; and, AFF, the dynamic LDS aff_dyn.
   if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   // consecutive workgroups land on the 8 XCDs round-robin: give each XCD a
@@ -44,9 +44,22 @@
   // deferred residues (ResCarry): one-feature waves, exact sums, default gain
   // (band mode too: the residue's rows were checked against the band at frame
   // j's final position, and an escape voids the whole chunk anyway)
-  const bool merge = !FB && G == 1 && EXACT && !LI && a.merge_res && a.nlev >= 2;
+  const bool merge = !FB && !AFF && G == 1 && EXACT && !LI && a.merge_res && a.nlev >= 2;
   ResCarry<PPL> rc;
   TrkCount cnt;
+  // affine check: the feature's six values and its window state stay in
+  // (wave-uniform) registers for the launch
+  float aff6[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  int ast = 0;
+  if constexpr (AFF) {
+    static_assert(G == 1, "the affine stage is wave-uniform: one feature per wave");
+    if (exists) {
+#pragma unroll
+      for (int q = 0; q < 6; ++q) aff6[q] = uni<G>(af.aff[6 * (long)f + q]);
+      ast = uni<G>(af.state[f]);
+      if (af.fresh) ast = ast != 0 ? 1 : 0;  // held from before the call
+    }
+  }
   for (int j = 0; j < b.nframes; ++j) {
     const bool job = rc.pending;  // frame j-1 is tentatively tracked at (x, y)
     const bool live = exists && (v >= 0 || job);  // lost features are not tracked (:1346)
@@ -86,6 +99,47 @@
       }
       if (fb.err && head) fb.err[j * fb.stride + f] = e;
     }
+    if constexpr (AFF) {
+      // the reference's record stage (trackFeatures.c:1438-1497) for a feature
+      // frame j's translation step left TRACKED (no deferred residue: its
+      // verdict is final), on level 0 as planes; every operand is wave-uniform
+      if (exists) {
+        if (live && v == kTracked) {
+          const TrkLevel P = j == 0 ? a.A[0] : at_frame(a.B[0], (long)(j - 1) * b.lfs[0]);
+          const TrkLevel Q = at_frame(a.B[0], (long)j * b.lfs[0]);
+          const AffImg I1{P.img, P.gx, P.gy, P.w, P.h}, I2{Q.img, Q.gx, Q.gy, Q.w, Q.h};
+          const int S = (af.p.ww + 2) * (af.p.wh + 2);
+          float *lds = aff_dyn + wave * af.lds_wave;
+          const int was = ast;
+          int status;
+          ast = aff_stage<kAffChunk>(lds, lds + af.lds_wave - aff::SOLVE, af.p, I1, I2,
+                                     af.store + (size_t)f * 3 * S, aff6, xp, yp, x, y, ast, lane, status);
+          if (status != kTracked) {
+            x = -1.0f;
+            y = -1.0f;
+            v = status;
+          }
+          if (was == 0) {
+            // the window this wave just stored is read from the next frame on,
+            // each lane reading what other lanes wrote (and lines that hold a
+            // neighbour's window too): stores complete, stale lines dropped
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+          }
+        } else {
+          ast = 0;  // lost by the translation step, now or before: no window
+        }
+        if (head) {
+          if (af.tab_aff) {
+            float *row = af.tab_aff + 6 * ((long)j * af.stride + f);
+#pragma unroll
+            for (int q = 0; q < 6; ++q) row[q] = aff6[q];
+          }
+          if (af.tab_state) af.tab_state[(long)j * af.stride + f] = ast;
+        }
+      }
+    }
     PROF_ADD(4, t_f0);
     if (job) {  // frame j-1's verdict came with frame j's first pass
       if (rstat != kTracked) {
@@ -109,6 +163,11 @@
     fx[f] = x;
     fy[f] = y;
     fv[f] = v;
+    if constexpr (AFF) {
+#pragma unroll
+      for (int q = 0; q < 6; ++q) af.aff[6 * (long)f + q] = aff6[q];
+      af.state[f] = ast;
+    }
     if (b.count) {  // one pair of atomics per feature per launch, spread over kCountSlots addresses
       const int k = (blk * (kBlock / kWave) + wave) & (kCountSlots - 1);
       atomicAdd(&b.count[k], (unsigned long long)cnt.solves);

@@ -33,6 +33,23 @@ class TrackDesc(C.Structure):
                 ("lighting_insensitive", C.c_int), ("reduction", C.c_int)]
 
 
+class AffineDesc(C.Structure):
+    """klt_hip_affine_desc: the affine consistency check's parameters."""
+    _fields_ = [("mode", C.c_int), ("window_width", C.c_int), ("window_height", C.c_int),
+                ("max_iterations", C.c_int), ("min_determinant", C.c_float),
+                ("min_displacement", C.c_float), ("affine_min_displacement", C.c_float),
+                ("max_residue", C.c_float), ("max_displacement_differ", C.c_float),
+                ("step_factor", C.c_float), ("lighting_insensitive", C.c_int)]
+
+    @classmethod
+    def from_tc(cls, tc) -> "AffineDesc":
+        """What KLTTrackFeatures passes for this tracking context (a TrackingContextRec)."""
+        return cls(tc.affineConsistencyCheck, tc.affine_window_width, tc.affine_window_height,
+                   tc.affine_max_iterations, tc.min_determinant, tc.min_displacement,
+                   tc.affine_min_displacement, tc.affine_max_residue, tc.affine_max_displacement_differ,
+                   tc.step_factor, tc.lighting_insensitive)
+
+
 class SelectDesc(C.Structure):
     _fields_ = [("window_width", C.c_int), ("window_height", C.c_int), ("borderx", C.c_int),
                 ("bordery", C.c_int), ("nSkippedPixels", C.c_int)]
@@ -74,6 +91,16 @@ DEVICE_PROTOS = {
     "klt_hip_set_fb": (C.c_int, [V, C.c_int, C.c_float]),
     "klt_hip_get_fb": (C.c_int, [V, IP, FP]),
     "klt_hip_set_fb_table": (C.c_int, [V, V, C.c_long]),
+    "klt_hip_set_frames_affine": (C.c_int, [V, C.POINTER(AffineDesc), V, V]),
+    "klt_hip_get_frames_affine": (C.c_int, [V, IP]),
+    "klt_hip_set_affine_table": (C.c_int, [V, V, V, C.c_long]),
+    "klt_hip_affine_state_put": (C.c_int, [V, FP, IP, C.c_int, C.POINTER(V), C.POINTER(V)]),
+    "klt_hip_affine_state_get": (C.c_int, [V, FP, IP, C.c_int]),
+    "klt_hip_affine_reserve": (C.c_int, [V, C.c_int, C.c_int, C.c_int]),
+    "klt_hip_affine_put": (C.c_int, [V, IP, C.c_int, FP]),
+    "klt_hip_affine_get": (C.c_int, [V, IP, C.c_int, FP]),
+    "klt_hip_track_affine": (C.c_int, [V, C.c_int, C.c_int, C.POINTER(TrackDesc), C.POINTER(AffineDesc), FP, FP, IP,
+                                       FP, IP, C.c_int]),
     "klt_hip_set_track_count": (C.c_int, [V, C.c_int]),
     "klt_hip_get_track_count": (C.c_int, [V, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_int]),
     "klt_hip_set_prof": (C.c_int, [V, V]),
@@ -98,6 +125,9 @@ DEVICE_PROTOS = {
     "klt_hip_frames_end_slot": (C.c_int, [V, C.c_int]),
     "klt_hip_track_frames": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc), V, C.c_long, C.c_long,
                                        C.c_int, C.c_int, V, V, V, C.c_int, V, V, V, C.c_long]),
+    # frames: const unsigned char *const *; rows: klt_hip_rows_fn or NULL
+    "klt_hip_track_frames_host": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc), V, C.c_int, C.c_int,
+                                            C.c_int, V, V, V, C.c_int, V, V]),
     "klt_hip_track_frames_band": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc), V, C.c_long, C.c_long,
                                             C.c_int, V, V, V, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, V,
                                             V, C.c_int]),
