@@ -241,9 +241,45 @@ size_t klt_hip_get_bank_budget(klt_hip_ctx *ctx);
 int klt_hip_frames_chunk(klt_hip_ctx *ctx);
 /* device bytes the context holds (pyramid slots, banks, upload ring, maps) */
 size_t klt_hip_ctx_footprint(klt_hip_ctx *ctx);
-/* klt_hip_track_frames scheduling: 1 builds chunk c+1's pyramids on a second
-   stream while chunk c is tracked; 0 (default) runs both on the context stream. */
+/* The schedule of a klt_hip_track_frames call that spans several chunks (a
+   call of one chunk, and each chunk of klt_hip_track_frames_host, stays on the
+   context stream; band calls always use both streams).  Results are the same,
+   bit for bit, in every schedule; klt_hip_ctx_reset restores 0.
+     0  one stream (default): each chunk's pyramids, then its tracker.
+     1  automatic: the library picks per call.  Lazy-gradient calls
+        (klt_hip_set_lazy_grad), whose tracker fills the register file so
+        that pyramid waves beside it only slow both down, take 3; every other
+        call takes 2.
+     2  beside: chunk c+1's pyramids are built on a second stream as soon as
+        their bank is free, for the whole length of chunk c's tracker.
+     3  tail: as 2, but the build is also held back until at most
+        klt_hip_set_frames_tail waves of chunk c's tracker are still running:
+        every wave of the launch adds 1 to a device counter as it leaves, the
+        one that brings it to the threshold writes it to signal memory, and
+        the second stream waits for that value (hipStreamWaitValue32).  The
+        events of 2 remain the dependencies, the counter is only a release
+        hint.  Only the lazy-gradient tracker kernels count (twin instances,
+        k_track7_hook); calls tracked by any other kernel run as in 2.
+   Anything else fails.  KLT_FRAMES_SCHED=0..3 in the environment replaces the
+   value for every context of the process (A/B in one tree). */
 int klt_hip_set_frames_overlap(klt_hip_ctx *ctx, int overlap);
+/* schedule 3: the tracker waves that may still be running when the next
+   chunk's build is released (default 3072, three per SIMD; 0: none, the build
+   follows the tracker).  A launch of no more waves than this is not waited
+   for.  KLT_FRAMES_TAIL=K in the environment replaces it. */
+int klt_hip_set_frames_tail(klt_hip_ctx *ctx, int waves_left);
+/* schedule 3's arithmetic, host only: with `base` exits counted before a launch
+   of `launched` waves, returns 1 and the counter value to wait for in
+   *threshold (base + launched - waves_left, so 1 <= *threshold - base <=
+   launched), or 0 (nothing to wait for) when launched <= waves_left. */
+int klt_hip_tail_threshold(unsigned base, unsigned launched, unsigned waves_left, unsigned *threshold);
+/* measurement hook, off (NULL) by default: a device buffer of 4 + 2 * cap
+   u64, zeroed but for [2] = cap, that every k_track7 launch fills with its
+   waves' wall_clock64() (100 MHz) times: [0] / [1] count the waves that have
+   entered / left, [4 + k] is the k-th entry time and [4 + cap + k] the k-th
+   exit time, each list in time order and not paired (the sum of the wave
+   durations is the difference of the two sums). */
+int klt_hip_set_wave_times(klt_hip_ctx *ctx, void *dev);
 /* 1 if pyramids for `desc` would be built by the fused gfx950 kernels, else 0 */
 int klt_hip_fused_path(klt_hip_ctx *ctx, const klt_hip_pyr_desc *desc);
 /* 1 if the slot was built by the fused gfx950 kernels, 0 generic, <0 invalid */

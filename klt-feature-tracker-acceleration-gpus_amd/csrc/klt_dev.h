@@ -146,6 +146,20 @@ struct TrkFramesArgs {
   int *tv;
   long tstride;  // table row stride (elements); tx == nullptr: no table
   unsigned long long *count;  // non-null: [kCountSlots] 2x2 systems formed, [kCountSlots] gather round trips
+  // k_track7's lazy-gradient instances with HOOK only (launch_track7 picks them
+  // when either pointer is set; the others never read these fields).
+  // exits: every launched wave adds 1 as it leaves, the waves that return
+  // before tracking too; the wave that brings the count to exit_thr writes
+  // that value to exit_sig, signal memory a stream can wait on: "all but K
+  // waves of this launch are gone" (klt_hip_set_frames_overlap's tail
+  // schedule).  The count itself is in device memory: 5024 system-scope adds
+  // to signal memory took 4.6 ms per launch.
+  // wave_t: {entered, left, capacity, 0}, then `capacity` entry times and
+  // `capacity` exit times (wall_clock64), each list in arrival order
+  // (klt_hip_set_wave_times)
+  unsigned *exits, *exit_sig;
+  unsigned exit_thr;
+  unsigned long long *wave_t;
 };
 // forward-backward check (klt_hip_set_fb): the FB kernel instances take this
 // beside TrkFramesArgs, so the FB-off instances keep their argument layout

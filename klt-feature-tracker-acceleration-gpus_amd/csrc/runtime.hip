@@ -253,6 +253,39 @@ static size_t copy_piece() {
   return n;
 }
 
+// klt_hip_set_frames_overlap's values
+enum { kSchedOne = 0, kSchedAuto = 1, kSchedBeside = 2, kSchedTail = 3 };
+// klt_hip_set_frames_tail's default: three of a SIMD's five lazy-gradient
+// tracker waves (256 CUs x 4 SIMDs), which leaves registers for three pyramid
+// waves beside them.  1080p / 5000, headline frames/s over one stream: K = 512
+// 1.00, 1024 1.03, 2048 1.05, 3072 and 3584 1.06; 4096 and 4608 1.07 in the
+// median but with single runs back at one stream's speed
+// (profiles/sched_tail_bound.txt)
+constexpr int kTailLeftDefault = 3072;
+// the exit counter is re-based (at a drained point) once it has passed this;
+// past it, and for launches of this many features, no launch counts, so the
+// count stays below 2^31 whatever the call's length
+constexpr unsigned kExitsRebase = 1u << 29;
+
+// A/B in one tree: KLT_FRAMES_SCHED=0..3 replaces whatever
+// klt_hip_set_frames_overlap was given, KLT_FRAMES_TAIL=K whatever
+// klt_hip_set_frames_tail was (-1: not set)
+static int env_frames_sched() {
+  static const int v = [] {
+    const char *e = getenv("KLT_FRAMES_SCHED");
+    return e && *e >= '0' && *e <= '3' && !e[1] ? *e - '0' : -1;
+  }();
+  return v;
+}
+static int env_frames_tail() {
+  static const int v = [] {
+    const char *e = getenv("KLT_FRAMES_TAIL");
+    const long x = e && *e ? atol(e) : -1;
+    return (int)(x < 0 ? -1 : x > (1 << 30) ? (1 << 30) : x);
+  }();
+  return v;
+}
+
 struct klt_hip_ctx {
   int device = 0;
   hipStream_t own = nullptr;
@@ -341,8 +374,21 @@ struct klt_hip_ctx {
   // caller queues between two chunks (klt_hip_set_ahead_ready)
   int ahead_ready = 0;
   hipEvent_t ev_go = nullptr;
-  int serial_frames = 1;  // klt_hip_track_frames: 1 builds and tracks on one stream (default: the
-                          // tracker and the pyramid kernels compete for the same CUs; overlap buys ~3 %)
+  // klt_hip_set_frames_overlap: the schedule of a plain batched call that spans
+  // several chunks (kSchedOne .. kSchedTail; track_frames_impl states the rule
+  // behind kSchedAuto)
+  int frames_sched = 0;
+  // the tail schedule: the next chunk's build is released when at most this
+  // many waves of the running tracker are left (klt_hip_set_frames_tail)
+  int tail_left = kTailLeftDefault;
+  // the tracker waves that have left, all launches of this context that were
+  // asked to count (TrkFramesArgs::exits, device memory), and the 8-byte signal
+  // allocation the pyramid stream waits on, which receives the count each time
+  // it reaches a launch's threshold; exits_base is the count once everything
+  // enqueued so far has run
+  unsigned *d_exits = nullptr, *d_exit_sig = nullptr;
+  unsigned exits_base = 0;
+  unsigned long long *wave_t = nullptr;  // klt_hip_set_wave_times: TrkFramesArgs::wave_t of k_track7 launches
   int *d_perm = nullptr;
   size_t perm_cap = 0;
   int perm_n = -1, perm_age = 0;  // features of the order in d_perm (-1: none), frames tracked with it
@@ -924,10 +970,17 @@ struct AffCall {
 };
 
 // ordered: the caller ran order_features into b already; fb_row: the
-// forward-backward / affine table row of this launch's first frame
+// forward-backward / affine table row of this launch's first frame; tail:
+// non-null asks for the exit count (the tail schedule), see TailRelease
+struct TailRelease {
+  unsigned left;  // in: the waves that may still be running at the release
+  bool wait;      // out: the launch counts, and c->d_exit_sig reaches thr when only `left` of its waves remain
+  unsigned thr;
+};
 int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc *d, const TrkArgs &a,
                         const TrkFramesArgs &b, float *x, float *y, int *v, int n, const float *own = nullptr,
-                        bool ordered = false, long fb_row = 0) {
+                        bool ordered = false, long fb_row = 0, TailRelease *tail = nullptr) {
+  if (tail) tail->wait = false;
   if (fb_refused(c, d, own != nullptr || a.escape != nullptr, "track")) return -1;
   if (aff_refused(c, d, own != nullptr || a.escape != nullptr, n, "track")) return -1;
   if (c->fb_on && c->fb_tab && c->fb_stride < n)
@@ -982,8 +1035,28 @@ int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc
     fb.stride = c->fb_stride;
   }
   const TrkFbArgs *fbp = c->fb_on ? &fb : nullptr;
-  if (t7)
-    return launched(c, "k_track7", launch_track7(st, aa.escape != nullptr, aa, b2, x, y, v, n, &c->track_kernel, fbp));
+  if (t7) {
+    // the lazy-gradient instances have twins that count and take times
+    if (aa.lazy && aa.aos) bb.wave_t = c->wave_t;
+    if (tail && aa.lazy && aa.aos && c->d_exits && !bb.n_dev) {
+      const int per = kBlock / kWave, nb = (n + per - 1) / per;
+      const unsigned waves = (unsigned)(bb.xcd_per > 0 ? 8 * bb.xcd_per : nb) * per;  // launch_track7's grid
+      tail->wait = klt_hip_tail_threshold(c->exits_base, waves, tail->left, &tail->thr) != 0;
+      if (tail->wait) {  // a launch of no more than `left` waves does not count at all
+        bb.exits = c->d_exits;
+        bb.exit_sig = c->d_exit_sig;
+        bb.exit_thr = tail->thr;
+        c->exits_base += waves;
+      }
+    }
+    const int rc =
+        launched(c, "k_track7", launch_track7(st, aa.escape != nullptr, aa, b2, x, y, v, n, &c->track_kernel, fbp));
+    if (rc && tail && tail->wait) {  // counted on the host, maybe not on the device: no wait, and re-base next time
+      tail->wait = false;
+      c->exits_base = kExitsRebase + 1;
+    }
+    return rc;
+  }
   TrkAffArgs af{};
   if (c->aff_on) {
     af.p = c->aff_p;
@@ -1284,6 +1357,11 @@ void exit_release_host(klt_hip_ctx *c) {
   c->h_stage = nullptr;
   c->h_rows = nullptr;
   c->stage_cap = c->hrows_cap = 0;
+  for (unsigned **p : {&c->d_exits, &c->d_exit_sig}) {  // the device is drained, nothing waits on the signal
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  c->exits_base = 0;
 }
 
 void exit_hook() {
@@ -1433,6 +1511,8 @@ KLT_API void klt_hip_ctx_destroy(klt_hip_ctx *c) {
   if (c->ev_caller) hipEventDestroy(c->ev_caller);
   if (c->ev_go) hipEventDestroy(c->ev_go);
   for (unsigned *p : c->d_sig) hipFree(p);
+  hipFree(c->d_exits);
+  hipFree(c->d_exit_sig);
   if (c->own) hipStreamDestroy(c->own);
   delete c;
 }
@@ -1517,7 +1597,9 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->aff_tab_stride = 0;
   c->aff_fresh = 1;
   c->aff_depth = 0;
-  c->serial_frames = 1;
+  c->frames_sched = kSchedOne;
+  c->tail_left = kTailLeftDefault;
+  c->wave_t = nullptr;
   c->ahead_ready = 0;
   c->prof = nullptr;
   c->frames_ready = false;
@@ -1796,7 +1878,33 @@ KLT_API int klt_hip_set_ahead_ready(klt_hip_ctx *c, int ready) {
 
 KLT_API int klt_hip_set_frames_overlap(klt_hip_ctx *c, int overlap) {
   if (!c) return fail(c, "set_frames_overlap: null context");
-  c->serial_frames = overlap ? 0 : 1;
+  if (overlap < kSchedOne || overlap > kSchedTail)
+    return fail(c, "set_frames_overlap: schedule %d (0 one stream, 1 automatic, 2 beside, 3 tail)", overlap);
+  c->frames_sched = overlap;
+  return 0;
+}
+
+KLT_API int klt_hip_set_frames_tail(klt_hip_ctx *c, int waves_left) {
+  if (!c) return fail(c, "set_frames_tail: null context");
+  if (waves_left < 0) return fail(c, "set_frames_tail: %d waves left", waves_left);
+  c->tail_left = waves_left;
+  return 0;
+}
+
+// base + launched - waves_left, the counter value at which at most waves_left
+// of the `launched` waves counted on top of `base` are still to leave; 0 (no
+// wait) when that many may be left from the start.  1 <= *threshold - base <=
+// launched: reached by the launch's own completion at the latest, never before
+// its first wave has left.
+KLT_API int klt_hip_tail_threshold(unsigned base, unsigned launched, unsigned waves_left, unsigned *threshold) {
+  if (launched == 0 || launched <= waves_left) return 0;
+  if (threshold) *threshold = base + (launched - waves_left);
+  return 1;
+}
+
+KLT_API int klt_hip_set_wave_times(klt_hip_ctx *c, void *dev) {
+  if (!c) return fail(c, "set_wave_times: null context");
+  c->wave_t = (unsigned long long *)dev;
   return 0;
 }
 
@@ -2567,7 +2675,57 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
   // stream: the cross-queue event hand-off would only add its latency
   // (~12 us measured between k_pyr_l1's end and k_track7's start).  The next
   // call's pyramid stream still starts behind it (ev_start below).
-  const bool serial = band ? false : (c->serial_frames != 0 || nframes <= chunk);
+  //
+  // The schedule of a plain call over several chunks (klt_hip_set_frames_overlap):
+  //   one stream: build, track, build, track, no kernel shares the CUs;
+  //   beside:     the pyramid stream builds chunk c+1 as soon as its bank is free,
+  //               so for the whole of chunk c's tracker;
+  //   tail:       the same, but the build is also held until at most tail_left
+  //               waves of chunk c's tracker are still to leave (its exit count
+  //               in c->d_exits), so it fills the CUs the tracker's last waves
+  //               leave empty and does not run beside a full tracker.
+  // Results are the same in all three.  The rule behind "automatic":
+  // A lazy-gradient call's tracker is held to 96 VGPRs for five waves per SIMD;
+  // 5 x 96 leaves 32 of a SIMD's 512 registers per lane and a pyramid wave needs
+  // 64, so beside a full tracker the build only gets the slots that open here
+  // and there, both kernels run slower for the tracker's whole length and the
+  // next tracker waits for the slow build.  A quarter of the tracker's wave
+  // slots stand empty over its launch, though, nearly all of them in its last
+  // third, so those calls take "tail".  1080p / 5000, six alternating runs
+  // each: one stream 84.6 k frames/s, beside 75.7 k, tail 89.8 k (its slowest run
+  // above one stream's fastest).  4K / 20 000, whose waves never all reside at
+  // once: one stream 22.3 k, beside 23.0 k, tail 23.0 k for every K from 2048 to
+  // 8192 -- nothing to tell tail from beside, so the rule does not look at the
+  // launch's size ("The schedule after lazy gradients";
+  // profiles/sched_tail_bound.txt).  A launch of no more waves than tail_left
+  // is not waited for, which is "beside" for a tracker that leaves room anyway.
+  // The other trackers (full records, the forward-backward and affine checks,
+  // fast sums on other depths, the generic kernel) leave room beside them, and
+  // "beside" measured 2-3 % faster there: they keep it.
+  constexpr int kAutoLazy = kSchedTail;
+  int sched = env_frames_sched() >= 0 ? env_frames_sched() : c->frames_sched;
+  if (sched == kSchedAuto) sched = lazy ? kAutoLazy : kSchedBeside;
+  const bool serial = band ? false : (sched == kSchedOne || nframes <= chunk);
+  const bool tail = !band && !serial && sched == kSchedTail;
+  const unsigned tail_left = (unsigned)(env_frames_tail() >= 0 ? env_frames_tail() : c->tail_left);
+  if (tail) {
+    const bool fresh = !c->d_exits || !c->d_exit_sig;
+    if (!c->d_exits) HIPCHK(c, hipMalloc((void **)&c->d_exits, sizeof(unsigned long long)));
+    if (!c->d_exit_sig)
+      HIPCHK(c, hipExtMallocWithFlags((void **)&c->d_exit_sig, sizeof(unsigned long long), hipMallocSignalMemory));
+    if (fresh || c->exits_base > kExitsRebase) {
+      // re-based long before the 32-bit count wraps, with nothing running or waiting
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->pstream));
+      HIPCHK(c, hipMemsetAsync(c->d_exits, 0, sizeof(unsigned long long), c->stream));
+      HIPCHK(c, hipMemsetAsync(c->d_exit_sig, 0, sizeof(unsigned long long), c->stream));
+      c->exits_base = 0;
+    }
+  }
+  // the exit count at which the pyramid stream may start the next build: set
+  // by each counted tracker launch of this call, after it is enqueued
+  bool tail_wait = false;
+  unsigned tail_thr = 0;
   // the pyramid stream starts behind everything already queued on the
   // tracking stream -- except a band call's build-ahead when the caller has
   // said its frames are ready (klt_hip_set_ahead_ready): that waits for its
@@ -2632,6 +2790,12 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
     // one stream: stream order is the dependency (an event wait would add a queue barrier)
     if (!serial && !prebuilt && pstream_behind()) return -1;  // this chunk's own frames: behind the caller's work
     if (!serial && !prebuilt && !ahead) HIPCHK(c, hipStreamWaitEvent(ps, c->ev_bfree[bi], 0));
+    // tail: a hint on top of ev_bfree / ev_bbuilt, which stay the dependencies.
+    // The tracker that raises the count to tail_thr was enqueued in the
+    // previous round of this loop and reaches it by completing.
+    if (tail_wait)
+      HIPCHK(c, hipStreamWaitValue32(ps, c->d_exit_sig, tail_thr, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    tail_wait = false;
     if (prebuilt) {
       // ev_bbuilt[bi] was recorded after that build: the wait below orders it
     } else if (fz) {
@@ -2672,9 +2836,13 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
       if (!c->ev_go) HIPCHK(c, hipEventCreateWithFlags(&c->ev_go, hipEventDisableTiming));
       HIPCHK(c, hipEventRecord(c->ev_go, c->stream));
     }
-    if (n > 0 &&
-        track_frames_launch(c, c->stream, td, a, b, x, y, val, n, band ? band->own : nullptr, true, fb_row0 + j0))
+    TailRelease rel{tail_left, false, 0};
+    const bool count = tail && c->exits_base <= kExitsRebase && (unsigned)n < kExitsRebase;
+    if (n > 0 && track_frames_launch(c, c->stream, td, a, b, x, y, val, n, band ? band->own : nullptr, true,
+                                     fb_row0 + j0, count ? &rel : nullptr))
       return -1;
+    tail_wait = rel.wait;
+    tail_thr = rel.thr;
     HMARK("track");
     if (!serial && !ahead && c->prev.bank >= 0) HIPCHK(c, hipEventRecord(c->ev_bfree[c->prev.bank], c->stream));
     c->prev = PrevRef{bi, Fc - 1};

@@ -420,6 +420,26 @@ struct Counts {
 #endif
 };
 
+// The HOOK instances: every way out of the kernel body (track7_body.h) passes
+// wave_exit once per wave, and its entry wave_time(.., 0) -- the optional
+// times and the optional count of the waves that have left (TrkFramesArgs::
+// wave_t / ::exits).  The count is a scheduling hint: nothing in the kernel
+// waits for it, and the one store to signal memory (read by the command
+// processor, hipStreamWaitValue32) is relaxed at system scope.  The sum of the
+// wave durations and both time distributions need no pairing of the lists.
+__device__ __forceinline__ void wave_time(unsigned long long *wave_t, int which) {
+  const unsigned long long t = wall_clock64(), k = atomicAdd(&wave_t[which], 1ull), cap = wave_t[2];
+  if (k < cap) wave_t[4 + which * cap + k] = t;
+}
+__device__ __forceinline__ void wave_exit(const TrkFramesArgs &b, int lane) {
+  if (lane != 0) return;
+  if (b.wave_t) wave_time(b.wave_t, 1);
+  if (b.exits) {
+    const unsigned k = atomicAdd(b.exits, 1u) + 1u;
+    if (k == b.exit_thr) __hip_atomic_store(b.exit_sig, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 #ifdef KLT_TRACK_PROF
 #define T7_T(t) const unsigned long long t = clock64()
 #define T7_ADD(k, t0) cnt.c[k] += clock64() - (t0)
@@ -703,7 +723,21 @@ __global__ __launch_bounds__(kBlock, LAZY && NL == 2 ? 5 : LAZY ? 4 : 1) void k_
                                                    float *__restrict__ fy, int *__restrict__ fv, int n) {
   static_assert(!LAZY || (AOS && !BAND), "lazy gradients: whole-frame interleaved pyramids");
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF + (LAZY ? kPat : 0)];
-  constexpr bool FB = false;
+  constexpr bool FB = false, HOOK = false;
+  const TrkFbArgs fb{};
+#include "track7_body.h"
+}
+
+// the lazy-gradient instances with the exit count and the wave times
+// (TrkFramesArgs::exits / ::wave_t; track7_body.h's HOOK): kernels of their
+// own, so that every other instance stays the code it was
+template <int NL, bool FAST>
+__global__ __launch_bounds__(kBlock, NL == 2 ? 5 : 4) void k_track7_hook(TrkArgs a, TrkFramesArgs b,
+                                                                          float *__restrict__ fx,
+                                                                          float *__restrict__ fy,
+                                                                          int *__restrict__ fv, int n) {
+  __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF + kPat];
+  constexpr bool BAND = false, AOS = true, LAZY = true, FB = false, HOOK = true;
   const TrkFbArgs fb{};
 #include "track7_body.h"
 }
@@ -714,7 +748,7 @@ __global__ __launch_bounds__(kBlock) void k_track7_fb(TrkArgs a, TrkFramesArgs b
                                                       float *__restrict__ fx, float *__restrict__ fy,
                                                       int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
-  constexpr bool BAND = false, FAST = false, FB = true, LAZY = false;
+  constexpr bool BAND = false, FAST = false, FB = true, LAZY = false, HOOK = false;
 #include "track7_body.h"
 }
 
@@ -777,6 +811,19 @@ hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const T
       *name = a.fast ? "kltdev::k_track7<false, true, 2, true, true>"
               : two  ? "kltdev::k_track7<false, true, 2, false, true>"
                      : "kltdev::k_track7<false, true, 0, false, true>";
+    if (b.exits || b.wave_t) {
+      if (name)
+        *name = a.fast ? "kltdev::k_track7_hook<2, true>"
+                : two  ? "kltdev::k_track7_hook<2, false>"
+                       : "kltdev::k_track7_hook<0, false>";
+      if (a.fast)
+        hipLaunchKernelGGL((k_track7_hook<2, true>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y, v, n);
+      else if (two)
+        hipLaunchKernelGGL((k_track7_hook<2, false>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y, v, n);
+      else
+        hipLaunchKernelGGL((k_track7_hook<0, false>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y, v, n);
+      return hipGetLastError();
+    }
     if (a.fast)
       hipLaunchKernelGGL((k_track7<false, true, 2, true, true>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y, v, n);
     else if (two)

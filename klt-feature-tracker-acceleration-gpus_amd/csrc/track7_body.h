@@ -2,17 +2,25 @@
 // included inside each kernel: the FB-off kernels keep their by-value
 // arguments and compile to what they were before the forward-backward
 // instances existed.  The including kernel provides: the template parameters
-// BAND, AOS, NL, FAST, LAZY; constexpr bool FB; TrkArgs a; TrkFramesArgs b;
+// BAND, AOS, NL, FAST, LAZY, HOOK; constexpr bool FB; TrkArgs a; TrkFramesArgs b;
 // TrkFbArgs fb; fx, fy, fv, n; and the LDS array red_all.
   if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  if constexpr (HOOK)
+    if (b.wave_t && lane == 0) wave_time(b.wave_t, 0);
   if (b.n_dev) n = *b.n_dev;
   // XCD-major block order over the (band-sorted) features actually processed
   const int xcd_per = b.n_dev && b.xcd_per > 0 ? ((n + kWaves - 1) / kWaves + 7) / 8 : b.xcd_per;
-  if (xcd_per > 0 && (int)(blockIdx.x / 8) >= xcd_per) return;
+  if (xcd_per > 0 && (int)(blockIdx.x / 8) >= xcd_per) {
+    if constexpr (HOOK) wave_exit(b, lane);
+    return;
+  }
   const int blk = xcd_per > 0 ? (int)(blockIdx.x % 8) * xcd_per + (int)(blockIdx.x / 8) : (int)blockIdx.x;
   const int slot = blk * kWaves + wave;
-  if (slot >= n) return;  // whole wave; no workgroup barrier in this kernel
+  if (slot >= n) {  // whole wave; no workgroup barrier in this kernel
+    if constexpr (HOOK) wave_exit(b, lane);
+    return;
+  }
   const int f = u(b.perm ? b.perm[slot] : slot);
   float *red = red_all[wave];
   for (int i = lane; i < kRedF; i += kWave) red[i] = 0.0f;  // pads stay +0
@@ -175,3 +183,4 @@
       atomicAdd(&b.count[kCountSlots + k], (unsigned long long)cnt.passes);
     }
   }
+  if constexpr (HOOK) wave_exit(b, lane);

@@ -105,6 +105,9 @@ DEVICE_PROTOS = {
     "klt_hip_get_track_count": (C.c_int, [V, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_int]),
     "klt_hip_set_prof": (C.c_int, [V, V]),
     "klt_hip_set_frames_overlap": (C.c_int, [V, C.c_int]),
+    "klt_hip_set_frames_tail": (C.c_int, [V, C.c_int]),
+    "klt_hip_tail_threshold": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint)]),
+    "klt_hip_set_wave_times": (C.c_int, [V, V]),
     "klt_hip_set_host_threads": (C.c_int, [V, C.c_int]),
     "klt_hip_get_host_threads": (C.c_int, [V]),
     "klt_hip_set_path": (C.c_int, [V, C.c_int]),
