@@ -10,7 +10,6 @@
 #include <sched.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -333,11 +332,10 @@ inline int usable_cpus() {
 // through its OWN queued tasks beside the workers until its count of
 // unfinished tasks is zero, so no wait can deadlock and one caller's sort never
 // runs another's tasks on its thread.  While any sort is in progress an idle
-// worker spins on the queue (for up to spin_us() after its last task, by
-// default until the sort ends) instead of sleeping, so a queued half starts within a microsecond or so rather than
-// after a futex wake-up (the wake-ups cost more than the splits they were
-// waking for); past that, and between sorts, it sleeps until a task is
-// queued.  The pool grows to the largest worker count asked for and lives
+// worker spins on the queue (until the sort ends) instead of sleeping, so a
+// queued half starts within a microsecond or so rather than after a futex
+// wake-up (the wake-ups cost more than the splits they were waking for);
+// between sorts it sleeps until a task is queued.  The pool grows to the largest worker count asked for and lives
 // until shutdown(), which the library's exit hook calls (runtime.hip): its
 // workers are joined there, before the library's own exit-time teardown runs.
 template <class P>
@@ -351,26 +349,15 @@ struct Pool {
     const std::atomic<bool> *stop;  // an asynchronous sort nobody will read any more (nullptr: none)
   };
 
-  // how long an idle worker spins after its last task while a sort is in
-  // progress: round 4 spun for the whole sort, round 5 bounded it to 50 us and
-  // REPLACE lost 14 % (the host sort 380 -> 493 us: a worker that fell asleep
-  // during the caller's first partition step of a 49k-point segment paid a
-  // futex wake-up for every half); KLT_SORT_SPIN_US (A/B) overrides, < 0 =
-  // the whole sort
-  static double spin_us() {
-    static const double v = [] {
-      const char *e = std::getenv("KLT_SORT_SPIN_US");
-      return e && *e ? std::atof(e) : -1.0;
-    }();
-    return v;
-  }
+  // an idle worker spins for as long as a sort is in progress: round 4 spun
+  // for the whole sort, round 5 bounded it to 50 us after the worker's last
+  // task and REPLACE lost 14 % (the host sort 380 -> 493 us: a worker that
+  // fell asleep during the caller's first partition step of a 49k-point
+  // segment paid a futex wake-up for every half)
   static void pause() {
 #if defined(__x86_64__) || defined(__i386__)
     __builtin_ia32_pause();
 #endif
-  }
-  static double now_us() {
-    return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
   }
   std::mutex m;
   std::condition_variable cv, done;
@@ -397,10 +384,7 @@ struct Pool {
     return *p;
   }
   void grow(int workers) {
-    static const int cap = [] {  // KLT_SORT_NO_CLAMP=1 (A/B): the round-4 count, unclamped
-      const char *e = std::getenv("KLT_SORT_NO_CLAMP");
-      return e && *e == '1' ? 1 << 20 : usable_cpus() - 1;
-    }();
+    static const int cap = usable_cpus() - 1;
     if (workers > cap) workers = cap;
     std::lock_guard<std::mutex> lk(m);
     if (quit.load(std::memory_order_relaxed)) return;
@@ -432,21 +416,19 @@ struct Pool {
   }
   void unreserve_one() { claim(); }
   void work() {
-    double last = now_us();
     unsigned seen = gen.load(std::memory_order_relaxed);
     for (;;) {
       if (quit.load(std::memory_order_relaxed)) return;
       if (!claim()) {
-        if (hot.load(std::memory_order_acquire) > 0 && (spin_us() < 0 || now_us() - last < spin_us())) {
+        if (hot.load(std::memory_order_acquire) > 0) {
           for (int k = 0; k < 32; ++k) pause();
-        } else {  // no sort in progress, or none of its tasks for a while: sleep until a task comes
+        } else {  // no sort in progress: sleep until a task comes
           std::unique_lock<std::mutex> lk(m);
           cv.wait(lk, [this, seen] {
             return qn.load(std::memory_order_relaxed) > 0 || quit.load(std::memory_order_relaxed) ||
                    gen.load(std::memory_order_relaxed) != seen;
           });
           seen = gen.load(std::memory_order_relaxed);
-          last = now_us();
         }
         continue;
       }
@@ -458,7 +440,6 @@ struct Pool {
         q.pop_front();
       }
       run(t);
-      last = now_us();
     }
   }
   void submit(const Task &t) {

@@ -10,8 +10,12 @@
 //   affine.hip    k_affine (the affine consistency check, one frame pair per
 //                 launch); its per-feature stage is affine_dev.h, which
 //                 track.hip's k_track_frames_g_aff runs inside the batched launch
-//   runtime.hip   host side: device contexts, slots and banks, pipelines,
-//                 the klt_hip_* C ABI (include/klt_hip.h)
+//   runtime*.hip  host side, the klt_hip_* C ABI (include/klt_hip.h); the
+//                 units share runtime.h (the device context) and host_pool.h:
+//                 runtime.hip contexts, exit hook, uploads, setters, selection;
+//                 runtime_pyr.hip slots, banks and pyramid builds;
+//                 runtime_track.hip tracker launches, per-call and affine
+//                 entry points; runtime_frames.hip the batched calls
 //
 // Kernels stay internal to their file; the runtime reaches them through the
 // launch_* functions declared here, which return the launch's hipError_t.

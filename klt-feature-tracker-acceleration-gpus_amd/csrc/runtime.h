@@ -1,0 +1,416 @@
+// runtime.h -- what the units of the host runtime share (internal): the device
+// context and what it is made of, the helpers every unit uses, and the
+// functions one unit calls in another (klt_dev.h lists the units).
+#pragma once
+
+#include <sys/resource.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "host_pool.h"
+#include "klt_dev.h"
+#include "klt_hip.h"
+
+#define KLT_API extern "C" __attribute__((visibility("default")))
+
+// klt_hip_set_lazy_grad's default ("Level-0 gradients in the tracker")
+#ifndef KLT_LAZY_GRAD_DEFAULT
+#define KLT_LAZY_GRAD_DEFAULT 1
+#endif
+
+using namespace kltdev;
+
+// runtime_track.hip (exported, as before the split)
+int feat_stage_in(klt_hip_ctx *c, const float *x, const float *y, const int *val, int n);
+int feat_unpack(klt_hip_ctx *c, float *x, float *y, int *val, int n);
+
+// everything below is internal to the library: no dynamic symbols
+#pragma GCC visibility push(hidden)
+
+// A level's storage is one block of 3 * cap floats, img | gx | gy.  Built by
+// the fused kernels it holds the level interleaved (il: {gx, gy, img} per
+// pixel from img on, the form the default tracker reads); built by the
+// generic one-pass kernels it holds the three planes at img, gx and gy.
+struct Level {
+  int w = 0, h = 0;
+  float *img = nullptr, *gx = nullptr, *gy = nullptr;  // gx = img + cap, gy = img + 2 cap
+  size_t cap = 0;  // floats per plane
+  int il = 0;      // contents: kLayoutPlanes, kLayoutRec (interleaved) or kLayoutImg (the img plane alone)
+};
+
+// a slot's level, or frame f of a bank's (interleaved levels: img is the
+// frame's interleaved base, gx/gy null)
+inline TrkLevel level_view(const Level &L, long f = 0, int vlo = 0, int vhi = 1 << 30) {
+  const long n = (long)L.w * L.h;
+  if (L.il == kLayoutImg) return TrkLevel{L.img + f * n, nullptr, nullptr, L.w, L.h, vlo, vhi, kLayoutImg};
+  if (L.il) return TrkLevel{L.img + 3 * f * n, nullptr, nullptr, L.w, L.h, vlo, vhi, 1};
+  return TrkLevel{L.img + f * n, L.gx + f * n, L.gy + f * n, L.w, L.h, vlo, vhi, 0};
+}
+
+struct Slot {
+  int nlev = 0;
+  int ss = 1;
+  int fused = -1;
+  Level lv[KLT_HIP_MAX_LEVELS];
+};
+
+enum TimerClass { T_L0 = 0, T_L1, T_TRACK, T_EIG, T_GEN, T_N };
+
+// a batch of same-size pyramids: plane l of frame f at lv[l].img + f * w*h
+struct Bank {
+  int frames = 0;  // capacity in frames
+  int nlev = 0;
+  int ss = 1;
+  Level lv[KLT_HIP_MAX_LEVELS];
+  float *hs = nullptr;  // per-frame row pass of the sigma-3.6 smoothing (fused path)
+  size_t hs_cap = 0;
+  int vlo[KLT_HIP_MAX_LEVELS] = {}, vhi[KLT_HIP_MAX_LEVELS] = {};  // rows built (band mode: a subset)
+};
+
+// where the pyramid preceding the next batch lives
+struct PrevRef {
+  int bank = -1;  // -1: pyramid slot `slot`
+  int frame = 0;
+  int slot = KLT_HIP_MAX_SLOTS;  // the batch seed slot unless klt_hip_frames_begin_slot
+};
+
+// klt_hip_set_frames_overlap's values
+enum { kSchedOne = 0, kSchedAuto = 1, kSchedBeside = 2, kSchedTail = 3 };
+// klt_hip_set_frames_tail's default: three of a SIMD's five lazy-gradient
+// tracker waves (256 CUs x 4 SIMDs), which leaves registers for three pyramid
+// waves beside them.  1080p / 5000, headline frames/s over one stream: K = 512
+// 1.00, 1024 1.03, 2048 1.05, 3072 and 3584 1.06; 4096 and 4608 1.07 in the
+// median but with single runs back at one stream's speed
+// (profiles/sched_tail_bound.txt)
+constexpr int kTailLeftDefault = 3072;
+// the exit counter is re-based (at a drained point) once it has passed this;
+// past it, and for launches of this many features, no launch counts, so the
+// count stays below 2^31 whatever the call's length
+constexpr unsigned kExitsRebase = 1u << 29;
+
+struct __attribute__((visibility("default"))) klt_hip_ctx {  // its constructor is a dynamic symbol, as before the split
+  int device = 0;
+  hipStream_t own = nullptr;
+  hipStream_t stream = nullptr;
+  hipStream_t pstream = nullptr;  // pyramid stream of the pipelined sequence
+  hipEvent_t ev_built[KLT_HIP_MAX_SLOTS] = {};
+  hipEvent_t ev_free[KLT_HIP_MAX_SLOTS] = {};
+  hipEvent_t ev_start = nullptr;
+  // a caller's stream (klt_hip_set_stream): ev_caller is recorded on it when
+  // the context switches away from it, so a reset or destroy can wait for the
+  // work queued there even after the caller has destroyed the stream
+  hipEvent_t ev_caller = nullptr;
+  bool caller_pending = false;
+  Slot slot[KLT_HIP_MAX_SLOTS + 2];  // + the batch seed and scratch slots
+  uint8_t *d_u8[2] = {nullptr, nullptr};
+  uint8_t *h_u8[2] = {nullptr, nullptr};
+  hipEvent_t u8_done[2] = {nullptr, nullptr};
+  size_t u8_cap = 0;
+  int u8_w[2] = {0, 0}, u8_h[2] = {0, 0};
+  float *d_hs = nullptr;
+  size_t hs_cap = 0;
+  float *d_tmp[2] = {nullptr, nullptr};
+  size_t tmp_cap[2] = {0, 0};
+  // host-array tracking (klt.h calls): x | y | val in one device block and one
+  // pinned host block, so a call moves its feature list in one copy each way
+  float *d_fx = nullptr, *d_fy = nullptr;  // views into d_feat
+  int *d_fv = nullptr;
+  float *d_feat = nullptr, *h_feat = nullptr;
+  // klt_hip_track on host lists: 2 (default) two copy kernels move the pinned
+  // block h_feat to d_feat and back around the tracker (no copy engine, no
+  // copy-to-kernel hand-off, and the tracker's gathers of x/y/val stay on the
+  // device: 111 against 130 us per registered 1080p/5000 call); 1 the kernels
+  // use h_feat in place over the bus; 0 copy-engine copies
+  int feat_mode = 2;
+  size_t f_cap = 0;
+  int *d_eig = nullptr;
+  size_t eig_cap = 0;
+  SelEngine *sel = nullptr;  // select.hip: the lazy exact selection
+  // caller buffers registered with klt_hip_register_host (page-locked): frame
+  // uploads from inside one are one DMA from the caller's pages, no staging
+  std::vector<std::pair<const unsigned char *, size_t>> registered;
+  // affine consistency check: stored windows (3*aff_S floats per feature) and per-call arrays
+  float *d_aff_store = nullptr;
+  size_t aff_store_cap = 0;
+  int aff_S = 0;
+  float *d_aff = nullptr, *d_xp = nullptr, *d_yp = nullptr, *d_astage = nullptr;
+  size_t aff_cap = 0, xp_cap = 0, yp_cap = 0, astage_cap = 0;
+  int *d_astate = nullptr, *d_aidx = nullptr;
+  size_t astate_cap = 0, aidx_cap = 0;
+  std::string err;
+  int force_generic = 0;
+  int track_order = 0;  // 0: band-sorted, XCD-major processing order; 1: input order
+  int track_patch = 1;  // one-feature waves gather through a lane patch when the window fits
+  int track_merge = 1;   // defer finest-level residues into the next frame's first pass (ResCarry)
+  int lazy_grad = KLT_LAZY_GRAD_DEFAULT;  // klt_hip_set_lazy_grad: image-only level 0 in the banks of plain batched calls
+  RTaps lazy_gg, lazy_gd;  // the gradient taps of the last such call (a kept image-only frame is made whole with them)
+  int track_prio = 1;    // tracker waves at issue priority 3 (klt_hip_set_track_prio)
+  // planes of interleaved levels for the kernels that read planes (the generic
+  // tracker, the affine check): [0] image 1, [1] image 2 (a batch of frames)
+  float *pl_scr[2][KLT_HIP_MAX_LEVELS] = {};
+  size_t pl_cap[2][KLT_HIP_MAX_LEVELS] = {};
+  int track_impl = 0;    // 0: track7.hip for the default configuration, 1: the generic k_track_frames_g
+  const char *track_kernel = nullptr;  // instance name of the last tracker launch (klt_hip_track_kernel)
+  // forward-backward check (klt_hip_set_fb): off by default; the optional
+  // device table of squared return distances (klt_hip_set_fb_table)
+  int fb_on = 0;
+  float fb_dist = 0.0f;
+  float *fb_tab = nullptr;
+  long fb_stride = 0;
+  // affine check inside the tracker launch (klt_hip_set_frames_affine): the
+  // caller's device arrays, the optional tables (klt_hip_set_affine_table);
+  // aff_fresh: the next tracker launch is the first of its API call (windows
+  // held on entry are state 1), aff_depth: nesting of the entry points
+  int aff_on = 0;
+  AffParams aff_p{};
+  float *aff_dev = nullptr;
+  int *aff_state_dev = nullptr;
+  float *aff_tab = nullptr;
+  int *aff_stab = nullptr;
+  long aff_tab_stride = 0;
+  int aff_fresh = 1, aff_depth = 0;
+  // band calls: 1 = the next chunk's frames are ready when the call is made
+  // (not written by work still queued on the tracking stream), so its
+  // build-ahead waits for its bank and for this chunk's processing order
+  // (ev_go: the pyramids start with the tracker) -- not for whatever the
+  // caller queues between two chunks (klt_hip_set_ahead_ready)
+  int ahead_ready = 0;
+  hipEvent_t ev_go = nullptr;
+  // klt_hip_set_frames_overlap: the schedule of a plain batched call that spans
+  // several chunks (kSchedOne .. kSchedTail; plan_frames states the rule
+  // behind kSchedAuto)
+  int frames_sched = 0;
+  // the tail schedule: the next chunk's build is released when at most this
+  // many waves of the running tracker are left (klt_hip_set_frames_tail)
+  int tail_left = kTailLeftDefault;
+  // the tracker waves that have left, all launches of this context that were
+  // asked to count (TrkFramesArgs::exits, device memory), and the 8-byte signal
+  // allocation the pyramid stream waits on, which receives the count each time
+  // it reaches a launch's threshold; exits_base is the count once everything
+  // enqueued so far has run
+  unsigned *d_exits = nullptr, *d_exit_sig = nullptr;
+  unsigned exits_base = 0;
+  unsigned long long *wave_t = nullptr;  // klt_hip_set_wave_times: TrkFramesArgs::wave_t of k_track7 launches
+  int *d_perm = nullptr;
+  size_t perm_cap = 0;
+  int perm_n = -1, perm_age = 0;  // features of the order in d_perm (-1: none), frames tracked with it
+  int *d_count = nullptr;  // band mode: features owned in this chunk
+  unsigned long long *d_trk_count = nullptr;  // klt_hip_set_track_count: {solves, passes}, null when off
+  // klt_hip_track_frames_host: frames uploaded chunk by chunk.  Two slots per
+  // stage: pinned staging (filled by the pool), the device ring (one DMA per
+  // chunk on cstream), device table rows (written by the tracker) and pinned
+  // table rows (one D2H per chunk on dstream, then handed to the caller)
+  unsigned char *d_ring = nullptr, *h_stage = nullptr;
+  float *d_rows = nullptr, *h_rows = nullptr;
+  size_t ring_cap = 0, stage_cap = 0, drows_cap = 0, hrows_cap = 0;  // bytes
+  hipStream_t cstream = nullptr, dstream = nullptr;
+  hipEvent_t ev_ring_free[2] = {}, ev_dma[2] = {}, ev_tracked[2] = {}, ev_rows[2] = {};
+  HostPool *pool = nullptr;
+  int copy_threads = default_host_threads();  // pool workers besides the caller (0: the caller alone)
+  unsigned long long *prof = nullptr;  // instrumented build: per-wave tracker phase counters
+  Bank bank[3];  // views into bank_arena
+  void *bank_arena = nullptr;
+  size_t bank_arena_bytes = 0;
+  size_t bank_budget = 0;  // bytes the bank arena may take (klt_hip_set_bank_budget; 0: the default)
+  size_t dev_total = 0;    // the device's memory (queried once, for the default budget)
+  int chunk_used = 0;      // frames per bank of the last klt_hip_track_frames* call (budget-capped)
+  int bank_next = 0;
+  // band mode: a bank whose pyramids were built ahead, during the previous
+  // call's tracking (klt_hip_track_frames_band's next_frames); -1: none
+  struct {
+    int bank = -1, F = 0, row_lo = 0, row_hi = 0, il = 1;
+    const unsigned char *src = nullptr;
+    long stride = 0;
+  } pre;
+  PrevRef prev;
+  bool frames_ready = false;
+  hipEvent_t ev_bbuilt[3] = {}, ev_bfree[3] = {};
+  bool timing = false;
+  long frames_timed[T_N] = {};
+  std::vector<hipEvent_t> ev_pool;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_used[T_N];
+};
+
+constexpr auto fail = &kltdev::ctx_fail;
+
+#define HIPCHK(c, expr)                                                                \
+  do {                                                                                 \
+    hipError_t e_ = (expr);                                                            \
+    if (e_ != hipSuccess) return fail((c), "%s: %s", #expr, hipGetErrorString(e_));    \
+  } while (0)
+
+inline double wall_us() {
+  timespec ts;
+  clock_gettime(CLOCK_MONOTONIC, &ts);
+  return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
+}
+
+inline int use_device(klt_hip_ctx *c) {
+  HIPCHK(c, hipSetDevice(c->device));
+  return 0;
+}
+
+template <class T>
+int grow(klt_hip_ctx *c, T **p, size_t *cap, size_t n) {
+  if (*cap >= n && *p) return 0;
+  if (*p) HIPCHK(c, hipFree(*p));
+  *p = nullptr;
+  HIPCHK(c, hipMalloc((void **)p, sizeof(T) * (n ? n : 1)));
+  *cap = n;
+  return 0;
+}
+
+inline hipEvent_t take_event(klt_hip_ctx *c) {
+  if (!c->ev_pool.empty()) {
+    hipEvent_t e = c->ev_pool.back();
+    c->ev_pool.pop_back();
+    return e;
+  }
+  hipEvent_t e = nullptr;
+  if (hipEventCreate(&e) != hipSuccess) return nullptr;
+  return e;
+}
+
+#ifdef KLT_HOST_PROF  // experiment builds: CLOCK_MONOTONIC marks through one call, printed to stderr
+struct HostMarks {
+  long t[32];
+  const char *what[32];
+  int n = 0;
+  void mark(const char *w) {
+    timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    if (n < 32) {
+      t[n] = ts.tv_sec * 1000000000L + ts.tv_nsec;
+      what[n++] = w;
+    }
+  }
+  HostMarks();
+  ~HostMarks() {
+    cur() = nullptr;
+    for (int i = 1; i < n; ++i) fprintf(stderr, "hostmark %s %.2f us\n", what[i], (t[i] - t[i - 1]) * 1e-3);
+    if (n) fprintf(stderr, "hostmark enter_ns %ld\n", t[0]);
+  }
+  static HostMarks *&cur() {
+    static thread_local HostMarks *p = nullptr;
+    return p;
+  }
+};
+inline HostMarks::HostMarks() { cur() = this; }
+#define HMARK(w) hm_.mark(w)
+#define HMARK_IN(w) \
+  if (HostMarks::cur()) HostMarks::cur()->mark(w)
+#else
+#define HMARK(w) (void)0
+#define HMARK_IN(w) (void)0
+#endif
+
+// HIP events around one launch, recorded on the stream the kernel runs on
+struct TimedScope {
+  klt_hip_ctx *c;
+  int cls;
+  hipStream_t st;
+  hipEvent_t a = nullptr, b = nullptr;
+  TimedScope(klt_hip_ctx *c_, int cls_, hipStream_t st_, int frames = 1) : c(c_), cls(cls_), st(st_) {
+    if (!c->timing) return;
+    c->frames_timed[cls] += frames;
+    a = take_event(c);
+    b = take_event(c);
+    if (a) hipEventRecord(a, st);
+  }
+  ~TimedScope() {
+    if (!c->timing || !a || !b) return;
+    hipEventRecord(b, st);
+    c->ev_used[cls].push_back({a, b});
+  }
+};
+
+// the context's host pool, created on first use (thread creation can throw:
+// no exception crosses an extern "C" entry; without a pool the caller works alone)
+inline void ensure_pool(klt_hip_ctx *c) {
+  if (c->pool || c->copy_threads <= 0) return;
+  try {
+    c->pool = new HostPool(c->copy_threads);
+  } catch (...) {
+    c->pool = nullptr;
+    c->copy_threads = 0;
+  }
+}
+
+template <class Fn>
+int host_parallel(klt_hip_ctx *c, size_t n, Fn fn) {
+  try {
+    if (c->pool) {
+      const std::function<void(size_t)> f = fn;
+      c->pool->parallel(n, f);
+    } else {
+      for (size_t i = 0; i < n; ++i) fn(i);
+    }
+  } catch (...) {
+    return fail(c, "track_frames_host: host task failed (out of memory?)");
+  }
+  return 0;
+}
+
+inline int launched(klt_hip_ctx *c, const char *what, hipError_t e) {
+  if (e != hipSuccess) return fail(c, "launch %s: %s", what, hipGetErrorString(e));
+  return 0;
+}
+
+// an entry point that tracks: the first tracker launch inside the outermost
+// one is the call's first (TrkAffArgs::fresh)
+struct AffCall {
+  klt_hip_ctx *c;
+  explicit AffCall(klt_hip_ctx *ctx) : c(ctx) {
+    if (c && c->aff_depth++ == 0) c->aff_fresh = 1;
+  }
+  ~AffCall() {
+    if (c) --c->aff_depth;
+  }
+};
+
+// track_frames_launch: ordered: the caller ran order_features into b already;
+// fb_row: the forward-backward / affine table row of this launch's first
+// frame; tail: non-null asks for the exit count (the tail schedule)
+struct TailRelease {
+  unsigned left;  // in: the waves that may still be running at the release
+  bool wait;      // out: the launch counts, and c->d_exit_sig reaches thr when only `left` of its waves remain
+  unsigned thr;
+};
+
+// runtime.hip
+int ensure_pipeline(klt_hip_ctx *c);
+// runtime_pyr.hip
+bool fused_ok(const klt_hip_pyr_desc *d);
+int ensure_slot(klt_hip_ctx *c, int s, const klt_hip_pyr_desc *d);
+int build_pyramid_on(klt_hip_ctx *c, int s, const klt_hip_pyr_desc *d, const unsigned char *frame, long pitch,
+                     int buf, hipStream_t st);
+size_t bank_arena_bytes(const klt_hip_pyr_desc *d, int frames);
+void free_banks(klt_hip_ctx *c);
+size_t bank_budget_of(klt_hip_ctx *c);
+int budget_chunk(klt_hip_ctx *c, const klt_hip_pyr_desc *d);
+int ensure_banks(klt_hip_ctx *c, const klt_hip_pyr_desc *d, int frames);
+int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const uint8_t *src, long pitch,
+                     long stride, int F, hipStream_t st, int row_lo = 0, int row_hi = 1 << 30, int plane_lo = 0,
+                     int plane_hi = 1 << 30, int il = 1);
+// runtime_track.hip
+int check_window(klt_hip_ctx *c, const klt_hip_track_desc *d);
+void fill_trk_args(const klt_hip_track_desc *d, int nlev, int ss, int ncols, int nrows, TrkArgs &a);
+bool t7_tracks(const klt_hip_ctx *c, const klt_hip_track_desc *d);
+int order_features(klt_hip_ctx *c, hipStream_t st, int nrows, const float *y, const int *v, int n, int nframes,
+                   const float *own, TrkFramesArgs &bb);
+int fb_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const char *who);
+int aff_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, int n, const char *who);
+int track_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, int n, const char *who);
+int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc *d, const TrkArgs &a,
+                        const TrkFramesArgs &b, float *x, float *y, int *v, int n, const float *own = nullptr,
+                        bool ordered = false, long fb_row = 0, TailRelease *tail = nullptr);
+#pragma GCC visibility pop

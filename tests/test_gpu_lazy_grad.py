@@ -315,6 +315,31 @@ def test_call_in_another_layout_follows(gpu, seq640, second):
             assert np.array_equal(a[k][1].view(np.int32), OY[:, col].view(np.int32))
 
 
+def test_bank_reallocation_over_image_only_kept_frame(gpu, seq640):
+    """A lazy call of 4 frames at chunk 2, then one of 4 frames at chunk 4 on
+    the same, fresh context: the second call finds its banks too small while
+    the kept pyramid is an image-only frame of one of them, so that frame is
+    made whole in the seed slot and the banks are laid out again.  Equal, bit
+    for bit, to the 8 frames tracked by a fresh context in one call.  The
+    footprints show that the context came without banks and ends with banks
+    of 4 frames (three banks, 3 floats per level-0 pixel)."""
+    frames = seq640[0][:9]
+    h, w = frames[0].shape
+    foot = []
+
+    def hook(ctx, done=False):
+        foot.append(gpu.klt_hip_ctx_footprint(ctx))
+
+    gpu.klt_amd_release_cached_devices()
+    got = batch_sequence(gpu, frames, 256, [2, 4], calls=[4, 4], ctx_hook=hook)
+    assert foot[0] < 3 * 2 * w * h * 12 and foot[1] - foot[0] >= 3 * 4 * w * h * 12
+    gpu.klt_amd_release_cached_devices()
+    want = batch_sequence(gpu, frames, 256, [8])
+    for a, b in zip(got, want):
+        assert np.array_equal(a.view(np.int32), b.view(np.int32))
+    assert (got[2][-1] == 0).sum() > 25
+
+
 def test_track_and_replace_after_sequence(gpu, oracle):
     """KLTTrackSequence (image-only banks), then per-call KLTTrackFeatures and
     KLTReplaceLostFeatures -- the tracker and the selection map read the kept

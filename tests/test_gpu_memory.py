@@ -104,7 +104,7 @@ def test_reset_trims_and_restores_defaults(gpu):
     ctx2 = gpu.klt_amd_device_context(tc2)
     assert ctx2 == ctx  # the parked context is handed on
     assert gpu.klt_hip_ctx_footprint(ctx2) <= (2 << 30)
-    env = os.environ.get("KLT_AMD_HOST_THREADS")  # the library's default (runtime.hip), clamped to 0..16
+    env = os.environ.get("KLT_AMD_HOST_THREADS")  # the library's default (host_pool.h), clamped to 0..16
     assert gpu.klt_hip_get_host_threads(ctx2) == (min(max(int(env), 0), 16) if env else 7)
     gpu.KLTFreeTrackingContext(tc2)
     assert gpu.klt_amd_release_cached_devices() >= 1

@@ -2,7 +2,7 @@
 the per-call API"): a KLTTrackFeatures frame from pageable memory goes
 through the host pool into pinned staging and is DMAed in groups -- by
 default two, the first a quarter of the frame, each queued as soon as its
-pieces are copied (runtime.hip HostPool::parallel_groups).  The knobs are
+pieces are copied (host_pool.h HostPool::parallel_groups).  The knobs are
 read once per process, so each configuration runs in a child process; every
 configuration, and the registered-buffer path (one DMA from the caller's
 pages), must leave the same feature lists, at a size above the 1 MB split

@@ -10,8 +10,10 @@ O=$R/klt-feature-tracker-acceleration-gpus_amd/lib/obj
 T=$(mktemp -d)
 /opt/rocm/bin/hipcc -O1 -g --offload-arch=gfx950 -ffp-contract=off -std=c++17 -w -I$R/include -I$C \
   -Xarch_host -fsanitize=thread -c $C/runtime.hip -o $T/k.o
+# the rest of the host runtime and the kernels it launches, as built
+REST=$(for f in runtime_pyr runtime_track runtime_frames pyramid track track7 affine select; do echo $O/$f.o; done)
 /opt/rocm/lib/llvm/bin/clang++ -O1 -g -fsanitize=thread -c $R/tools/hostcheck/copy_pool_tsan.cpp -o $T/main.o
-/opt/rocm/lib/llvm/bin/clang++ -fsanitize=thread -o $T/t $T/main.o $T/k.o $O/pyramid.o $O/track.o $O/affine.o $O/klt_api.o $O/klt_io.o \
+/opt/rocm/lib/llvm/bin/clang++ -fsanitize=thread -o $T/t $T/main.o $T/k.o $REST $O/klt_api.o $O/klt_io.o \
   $O/klt_select.o $O/klt_synth.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lm -lpthread
 TSAN_OPTIONS=halt_on_error=1 $T/t
 rm -rf $T
