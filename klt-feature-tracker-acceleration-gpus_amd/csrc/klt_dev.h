@@ -3,7 +3,8 @@
 //
 //   pyramid.hip   k_pyr_l0 / k_pyr_l1 (fused default-parameter pyramid),
 //                 the generic one-pass kernels, k_min_eigen, k_synth
-//   track.hip     k_track_frames (the Newton loop), k_band_order
+//   track.hip     k_track_frames_g (the Newton loop for any window, one wave per
+//                 feature; the _g is only a name), k_band_order
 //   track7.hip    k_track7 (the Newton loop of the default configuration)
 //                 both with forward-backward instances (k_*_fb); the kernels'
 //                 bodies are track_body.h / track7_body.h

@@ -1,5 +1,5 @@
 // track.hip -- the Lucas-Kanade Newton loop of KLTTrackFeatures on gfx950:
-//   k_track_frames    _trackFeature (trackFeatures.c:381-486) inside the
+//   k_track_frames_g  _trackFeature (trackFeatures.c:381-486) inside the
 //                     coarse-to-fine level loop of KLTTrackFeatures
 //                     (:1343-1437), one wave64 per feature, carried through a
 //                     batch of frames
@@ -10,6 +10,8 @@
 #pragma clang fp contract(off)
 
 #include <math.h>
+
+#include <type_traits>
 
 #include "affine_dev.h"
 #include "klt_dev.h"
@@ -36,11 +38,8 @@ __device__ __forceinline__ f4 ld4(const float *p) { return *reinterpret_cast<con
 // l, l+64, ... (row-major index p = (j+hh)*ww + (i+hw)); interpolation runs in
 // parallel, the window sums are then accumulated in the reference's order by
 // lanes 0..NS-1 (one sum each) from an LDS staging area.
-// ---------------------------------------------------------------------------
-
-
-// ---------------------------------------------------------------------------
-// batched frames: each feature is carried through a batch of frames
+//
+// Batched frames: each feature is carried through a batch of frames
 // (the KLTTrackFeatures + KLTStoreFeatureList loop of example3.c:54-74 with
 // no replacement).  Frame j tracks pyramid j-1 -> j of the bank (j = 0: from
 // a.A, the pyramid before the batch); every feature is independent, so the
@@ -52,19 +51,10 @@ __device__ __forceinline__ TrkLevel at_frame(const TrkLevel &L, long off) {
   return TrkLevel{L.img + off, L.gx + off, L.gy + off, L.w, L.h, L.vlo, L.vhi};
 }
 
-// ---------------------------------------------------------------------------
-// Grouped tracker: G features per wave, 64/G lanes each (PPL pixels per lane).
-// The per-pixel work is the same per feature as one feature per wave, but the
-// wave-wide parts -- the 49-add ordered-sum chain, the 2x2 solve, the window
-// tests, loop control -- are shared by G features.  Features of a wave iterate
-// in lock step; a converged feature's lanes are masked until the wave's last
-// feature finishes the level.  Results are bit-identical: each feature's sums
-// are still formed by one lane in pixel order.
-// ---------------------------------------------------------------------------
 // Instrumented build (make prof): per-wave shader-clock cycles per phase
 #ifdef KLT_TRACK_PROF
 // kProfN counters: 0 gather+interp, 1 sums, 2 solve, 3 residue, 4 frame, 5 iterations, 6 passes, 7 wall ticks,
-// 8/9 wall start/end, 10 levels (track_level_g calls), 11 pass-top tests (window/escape/hand-over)
+// 8/9 wall start/end, 10 levels (track_level calls), 11 pass-top tests (window/escape/hand-over)
 struct Prof {
   unsigned long long c[kProfN] = {};
 };
@@ -81,13 +71,13 @@ struct Prof {
 #define PROF_INC(k)
 #endif
 
-// Lane <-> window pixel map.  Default: pixel p = l + LG*k (l = lane in the
-// feature's lane group).  PATCH (G = PPL = 1, (ww+1)*(wh+1) <= 64): lanes
+// Lane <-> window pixel map.  Default: lane l holds pixels p = l + 64*k,
+// k < PPL.  PATCH (PPL = 1, (ww+1)*(wh+1) <= 64): lanes
 // form a (ww+1)-wide patch, lane = j*(ww+1) + i holds pixel (i, j) of the
 // window for i < ww, j < wh; the extra column/row are the bilinear corners'
 // far side, so one 4-byte load per lane fetches every corner of every pixel.
-template <int G, int PPL, bool PATCH, int WIN>
-struct GroupWin {
+template <int PPL, bool PATCH, int WIN>
+struct LaneWin {
   int oi[PPL], oj[PPL];
   int p[PPL];  // pixel index in the reference's row-major order
   bool on[PPL];
@@ -95,12 +85,11 @@ struct GroupWin {
   int ci, cj;  // PATCH: this lane's patch cell
 };
 
-template <int G, int PPL, bool PATCH, int WIN>
-__device__ __forceinline__ GroupWin<G, PPL, PATCH, WIN> group_window(int ww_rt, int wh_rt, int lane) {
+template <int PPL, bool PATCH, int WIN>
+__device__ __forceinline__ LaneWin<PPL, PATCH, WIN> lane_window(int ww_rt, int wh_rt, int lane) {
   const int ww = WIN ? WIN : ww_rt, wh = WIN ? WIN : wh_rt;
-  constexpr int LG = kWave / G;
-  const int l = lane % LG, npx = ww * wh, hw = ww / 2, hh = wh / 2;
-  GroupWin<G, PPL, PATCH, WIN> w;
+  const int npx = ww * wh, hw = ww / 2, hh = wh / 2;
+  LaneWin<PPL, PATCH, WIN> w;
   w.pw = ww + 1;
   if (PATCH) {
     const int j = lane / (ww + 1), i = lane - j * (ww + 1);
@@ -114,7 +103,7 @@ __device__ __forceinline__ GroupWin<G, PPL, PATCH, WIN> group_window(int ww_rt, 
   }
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
-    const int p0 = l + LG * k;
+    const int p0 = lane + kWave * k;
     w.on[k] = p0 < npx;
     const int p = w.on[k] ? p0 : npx - 1;  // idle slots gather the last pixel's lines
     const int jj = p / ww;
@@ -125,26 +114,28 @@ __device__ __forceinline__ GroupWin<G, PPL, PATCH, WIN> group_window(int ww_rt, 
   return w;
 }
 
-// NS ordered sums per feature.  Pixel p of sum s goes to red[(g*NS+s)*rp + p];
-// entries [npx, rp) of every row are zeroed once per kernel (zero_red) and
+// NS ordered sums per feature.  Pixel p of sum s goes to red[s*rp + p];
+// entries [npx, rp) of every row are zeroed once per kernel (track_body.h) and
 // never written, so whole 16-byte chunks add exactly (acc + +0 == acc, an
-// ordered sum from +0 is never -0).  Lane g*NS+s then adds row g*NS+s in
-// pixel order: the reference's sequential float sum.
-template <int G, int NS, int PPL, bool PATCH, int WIN>
-__device__ __forceinline__ void exact_sums_g(const GroupWin<G, PPL, PATCH, WIN> &w, const float (&v)[NS][PPL],
-                                             float *red, int rp, int npx, int lane, float (&out)[NS]) {
-  constexpr int LG = kWave / G;
-  const int g = lane / LG;
+// ordered sum from +0 is never -0).  Lane s then adds row s in pixel order:
+// the reference's sequential float sum.
+// A wave's staging: up to six rows of kWave * PPL pixels + a 4-float pad, and
+// a tail pad for the batched reads past the last row.
+constexpr int red_floats(int ppl) { return 6 * (kWave * ppl + 4) + 16; }
+
+template <int NS, int PPL, bool PATCH, int WIN>
+__device__ __forceinline__ void exact_sums(const LaneWin<PPL, PATCH, WIN> &w, const float (&v)[NS][PPL],
+                                           float *red, int rp, int npx, int lane, float (&out)[NS]) {
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
     if (w.on[k]) {
 #pragma unroll
-      for (int s = 0; s < NS; ++s) red[(g * NS + s) * rp + w.p[k]] = v[s][k];
+      for (int s = 0; s < NS; ++s) red[s * rp + w.p[k]] = v[s][k];
     }
   }
   lds_wave_sync();
   float acc = 0.0f;
-  if (WIN > 0 && lane < G * NS) {
+  if (WIN > 0 && lane < NS) {
     // compile-time window: fully unrolled, exactly one add per pixel
     constexpr int NPX = WIN * WIN, NCH = (NPX + 3) / 4, B = KLT_SUM_BATCH;
     const float *r = red + lane * rp;
@@ -163,7 +154,7 @@ __device__ __forceinline__ void exact_sums_g(const GroupWin<G, PPL, PATCH, WIN> 
         if (q + 3 < NPX) acc += c[k].w;
       }
     }
-  } else if (lane < G * NS) {
+  } else if (lane < NS) {
     // B chunks per batch, read whole before the ordered adds; reads past the
     // row's last chunk land in the next row or the buffer's tail pad, unused
     const float *r = red + lane * rp;
@@ -184,20 +175,14 @@ __device__ __forceinline__ void exact_sums_g(const GroupWin<G, PPL, PATCH, WIN> 
       }
     }
   }
-  if (G == 1) {
 #pragma unroll
-    for (int s = 0; s < NS; ++s) out[s] = bcast(acc, s);
-  } else {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) out[s] = __shfl(acc, g * NS + s);
-  }
+  for (int s = 0; s < NS; ++s) out[s] = bcast(acc, s);
   lds_wave_sync();
 }
 
-template <int G, int NS, int PPL, bool PATCH, int WIN>
-__device__ __forceinline__ void tree_sums_g(const GroupWin<G, PPL, PATCH, WIN> &w, const float (&v)[NS][PPL],
-                                            float (&out)[NS]) {
-  constexpr int LG = kWave / G;
+template <int NS, int PPL, bool PATCH, int WIN>
+__device__ __forceinline__ void tree_sums(const LaneWin<PPL, PATCH, WIN> &w, const float (&v)[NS][PPL],
+                                          float (&out)[NS]) {
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
     float acc = 0.0f;
@@ -205,16 +190,16 @@ __device__ __forceinline__ void tree_sums_g(const GroupWin<G, PPL, PATCH, WIN> &
     for (int k = 0; k < PPL; ++k)
       if (w.on[k]) acc += v[s][k];
 #pragma unroll
-    for (int off = LG / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+    for (int off = kWave / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
     out[s] = acc;
   }
 }
 
-template <int G, int NS, int PPL, bool PATCH, int WIN, bool EXACT>
-__device__ __forceinline__ void sums_g(const GroupWin<G, PPL, PATCH, WIN> &w, const float (&v)[NS][PPL], float *red,
+template <int NS, int PPL, bool PATCH, int WIN, bool EXACT>
+__device__ __forceinline__ void sums(const LaneWin<PPL, PATCH, WIN> &w, const float (&v)[NS][PPL], float *red,
                                        int rp, int npx, int lane, float (&out)[NS]) {
-  if (EXACT) exact_sums_g<G, NS, PPL, PATCH, WIN>(w, v, red, rp, npx, lane, out);
-  else tree_sums_g<G, NS, PPL, PATCH, WIN>(w, v, out);
+  if (EXACT) exact_sums<NS, PPL, PATCH, WIN>(w, v, red, rp, npx, lane, out);
+  else tree_sums<NS, PPL, PATCH, WIN>(w, v, out);
 }
 
 // Bilinear samples of a level's planes for this lane's pixel(s).  PATCH: one
@@ -238,8 +223,8 @@ struct PatchCache {
   float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
 };
 
-template <int G, int PPL, bool PATCH, int WIN>
-__device__ __forceinline__ PatchPos patch_pos(const GroupWin<G, PPL, PATCH, WIN> &w, int nc, int nr, float x, float y) {
+template <int PPL, bool PATCH, int WIN>
+__device__ __forceinline__ PatchPos patch_pos(const LaneWin<PPL, PATCH, WIN> &w, int nc, int nr, float x, float y) {
   PatchPos q;
   const float xs = x + w.oi[0], ys = y + w.oj[0];
   const int xt = (int)xs, yt = (int)ys;
@@ -261,8 +246,8 @@ __device__ __forceinline__ float patch_load(const float *P, const PatchPos &q) {
   return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(P) + q.off);
 }
 
-template <int G, int PPL, bool PATCH, int WIN>
-__device__ __forceinline__ float patch_value(const GroupWin<G, PPL, PATCH, WIN> &w, const PatchPos &q, float v,
+template <int PPL, bool PATCH, int WIN>
+__device__ __forceinline__ float patch_value(const LaneWin<PPL, PATCH, WIN> &w, const PatchPos &q, float v,
                                              int lane) {
   const int pw = w.pw;
   const float v01 = __shfl(v, lane + 1), v10 = __shfl(v, lane + pw), v11 = __shfl(v, lane + pw + 1);
@@ -287,9 +272,9 @@ __device__ __forceinline__ float corner_interp(const Bil &b, const Corners &c) {
   return b.w0 * c.r0.x + b.w1 * c.r0.y + b.w2 * c.r1.x + b.w3 * c.r1.y;
 }
 
-template <int G, int PPL, bool PATCH, int WIN>
+template <int PPL, bool PATCH, int WIN>
 __device__ __forceinline__ void gather_direct2(const TrkLevel &A, const TrkLevel &B,
-                                               const GroupWin<G, PPL, PATCH, WIN> &w, float x1, float y1, float x2,
+                                               const LaneWin<PPL, PATCH, WIN> &w, float x1, float y1, float x2,
                                                float y2, bool first, bool grads, float (&a_im)[PPL],
                                                float (&a_gx)[PPL], float (&a_gy)[PPL], float (&b_im)[PPL],
                                                float (&b_gx)[PPL], float (&b_gy)[PPL]) {
@@ -339,8 +324,8 @@ struct ResCarry {
 };
 
 // residue job's img2 samples: rows of plane R at (rx, ry) + the window offsets
-template <int G, int PPL, bool PATCH, int WIN>
-__device__ __forceinline__ void residue_direct(const TrkLevel &R, const GroupWin<G, PPL, PATCH, WIN> &w, float rx,
+template <int PPL, bool PATCH, int WIN>
+__device__ __forceinline__ void residue_direct(const TrkLevel &R, const LaneWin<PPL, PATCH, WIN> &w, float rx,
                                                float ry, float (&r_b)[PPL]) {
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
@@ -349,8 +334,8 @@ __device__ __forceinline__ void residue_direct(const TrkLevel &R, const GroupWin
   }
 }
 
-template <int G, int PPL, bool PATCH, int WIN>
-__device__ __forceinline__ void residue_sample(const TrkLevel &R, const GroupWin<G, PPL, PATCH, WIN> &w, float rx,
+template <int PPL, bool PATCH, int WIN>
+__device__ __forceinline__ void residue_sample(const TrkLevel &R, const LaneWin<PPL, PATCH, WIN> &w, float rx,
                                                float ry, int lane, float (&r_b)[PPL]) {
   if constexpr (PATCH) {
     const PatchPos q = patch_pos(w, R.w, R.h, rx, ry);
@@ -373,9 +358,9 @@ __device__ __forceinline__ float direct_one(const float *__restrict__ P, const B
   return r;
 }
 
-template <int G, int PPL, bool PATCH, int WIN>
+template <int PPL, bool PATCH, int WIN>
 __device__ __forceinline__ void gather_direct_seq(const TrkLevel &A, const TrkLevel &B,
-                                                  const GroupWin<G, PPL, PATCH, WIN> &w, float x1, float y1,
+                                                  const LaneWin<PPL, PATCH, WIN> &w, float x1, float y1,
                                                   float x2, float y2, bool first, bool grads, float (&a_im)[PPL],
                                                   float (&a_gx)[PPL], float (&a_gy)[PPL], float (&b_im)[PPL],
                                                   float (&b_gx)[PPL], float (&b_gy)[PPL]) {
@@ -394,8 +379,8 @@ __device__ __forceinline__ void gather_direct_seq(const TrkLevel &A, const TrkLe
   }
 }
 
-template <int G, int PPL, bool PATCH, int WIN>
-__device__ __forceinline__ void gather_pass(const TrkLevel &A, const TrkLevel &B, const GroupWin<G, PPL, PATCH, WIN> &w,
+template <int PPL, bool PATCH, int WIN>
+__device__ __forceinline__ void gather_pass(const TrkLevel &A, const TrkLevel &B, const LaneWin<PPL, PATCH, WIN> &w,
                                             float x1, float y1, float x2, float y2, bool first, bool grads,
                                             int lane, float (&a_im)[PPL], float (&a_gx)[PPL], float (&a_gy)[PPL],
                                             float (&b_im)[PPL], float (&b_gx)[PPL], float (&b_gy)[PPL],
@@ -454,20 +439,18 @@ __device__ __forceinline__ void gather_pass(const TrkLevel &A, const TrkLevel &B
   }
 }
 
+// The flags it is applied to (act, fin, go, live) hold one value in all 64
+// lanes, so wave_any(p) == p; the ballots stay because the register allocation
+// is tuned around them: with plain booleans 22 of the 52 instances got more
+// VGPRs or SGPR spills, 6 of them one wave per SIMD fewer.
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
 
-// One feature per wave (G == 1): per-feature state is wave-uniform; pinning it
-// to scalar registers keeps the vector register file for the window pixels.
-template <int G>
+// Per-feature state is wave-uniform; pinning it to scalar registers keeps the
+// vector register file for the window pixels.
 __device__ __forceinline__ float uni(float v) {
-  if (G == 1) return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
-  return v;
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
-template <int G>
-__device__ __forceinline__ int uni(int v) {
-  if (G == 1) return __builtin_amdgcn_readfirstlane(v);
-  return v;
-}
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Work counters of a feature (klt_hip_track_counts): 2x2 systems formed --
 // the reference's Newton loop bodies (trackFeatures.c:418-455), the one that
@@ -476,9 +459,8 @@ struct TrkCount {
   unsigned solves = 0, passes = 0;
 };
 
-// _trackFeature (trackFeatures.c:381-486) for the G features of a wave at one
-// level.  Per-lane state is uniform within a feature's lane group; `live`
-// says whether the group's feature is tracked at this level.
+// _trackFeature (trackFeatures.c:381-486) for the wave's feature at one level;
+// `live` says whether the feature is tracked at this level.
 //
 // Latency layout: every global round trip gathers img2 at the current
 // position x2.  The img1 samples are gathered with the first of them, and the
@@ -487,11 +469,11 @@ struct TrkCount {
 // trips instead of k+2.  The order of tests is the reference's: window test
 // at the top of each iteration and once after the loop (same x2, same test),
 // SMALL_DET ends the loop before x2 moves, residue only for TRACKED.
-template <int G, int PPL, bool PATCH, int WIN, bool EXACT, bool LI, bool BAND>
-__device__ int track_level_g(PROF_DECL const TrkArgs &a, const GroupWin<G, PPL, PATCH, WIN> &w, const TrkLevel &A,
-                             const TrkLevel &B, float x1, float y1, float &x2, float &y2, bool live, int lane,
-                             float *red, bool residue, ResCarry<PPL> &rc, bool job, bool defer, const TrkLevel &R,
-                             int &rstat, TrkCount &cnt) {
+template <int PPL, bool PATCH, int WIN, bool EXACT, bool LI, bool BAND>
+__device__ int track_level(PROF_DECL const TrkArgs &a, const LaneWin<PPL, PATCH, WIN> &w, const TrkLevel &A,
+                           const TrkLevel &B, float x1, float y1, float &x2, float &y2, bool live, int lane,
+                           float *red, bool residue, ResCarry<PPL> &rc, bool job, bool defer, const TrkLevel &R,
+                           int &rstat, TrkCount &cnt) {
   // job: rc holds the previous frame's deferred residue (img2 plane R), done
   // in this level's first pass, verdict in rstat (the level stops when it
   // loses that frame's feature); defer: this (finest) level's own residue is
@@ -547,8 +529,8 @@ __device__ int track_level_g(PROF_DECL const TrkArgs &a, const GroupWin<G, PPL, 
     float b_im[PPL], b_gx[PPL], b_gy[PPL], r_b[PPL];
     const bool grads = wave_any(act && !fin);  // a residue-only pass needs img2 alone
     if (act) {  // img1 is sampled once per level, with the level's first img2 gather
-      gather_pass<G, PPL, PATCH, WIN>(A, B, w, x1, y1, x2, y2, first, grads, lane, a_im, a_gx, a_gy, b_im, b_gx,
-                                      b_gy, pcache, job, &R, rc.x2, rc.y2, r_b);
+      gather_pass<PPL, PATCH, WIN>(A, B, w, x1, y1, x2, y2, first, grads, lane, a_im, a_gx, a_gy, b_im, b_gx, b_gy,
+                                   pcache, job, &R, rc.x2, rc.y2, r_b);
     } else {
       if (job) residue_sample(R, w, rc.x2, rc.y2, lane, r_b);
 #pragma unroll
@@ -571,7 +553,7 @@ __device__ int track_level_g(PROF_DECL const TrkArgs &a, const GroupWin<G, PPL, 
         mom[2][k] = a_im[k] * a_im[k];
         mom[3][k] = b_im[k] * b_im[k];
       }
-      sums_g<G, 4, PPL, PATCH, WIN, EXACT>(w, mom, red, a.red_pitch, npx, lane, S);
+      sums<4, PPL, PATCH, WIN, EXACT>(w, mom, red, a.red_pitch, npx, lane, S);
       alpha = (float)sqrt((double)((S[2] / n) / (S[3] / n)));
       beta = S[0] / n - alpha * (S[1] / n);
       alpha_g = (float)sqrt((double)((S[0] / n) / (S[1] / n)));
@@ -587,7 +569,7 @@ __device__ int track_level_g(PROF_DECL const TrkArgs &a, const GroupWin<G, PPL, 
         const float d = LI ? (a_im[k] - b_im[k] * alpha - beta) : (a_im[k] - b_im[k]);
         dif[0][k] = res ? fabsf(d) : 0.0f;
       }
-      sums_g<G, 1, PPL, PATCH, WIN, EXACT>(w, dif, red, a.red_pitch, npx, lane, S);
+      sums<1, PPL, PATCH, WIN, EXACT>(w, dif, red, a.red_pitch, npx, lane, S);
       if (res) {
         if (S[0] / n > a.max_res) status = kLargeResidue;
         act = false;
@@ -609,7 +591,7 @@ __device__ int track_level_g(PROF_DECL const TrkArgs &a, const GroupWin<G, PPL, 
     if (!wave_any(act)) {
       if (job) {
         float S1[1];
-        sums_g<G, 1, PPL, PATCH, WIN, EXACT>(w, rdif, red, a.red_pitch, npx, lane, S1);
+        sums<1, PPL, PATCH, WIN, EXACT>(w, rdif, red, a.red_pitch, npx, lane, S1);
         verdict(S1[0]);
       }
       break;
@@ -650,13 +632,13 @@ __device__ int track_level_g(PROF_DECL const TrkArgs &a, const GroupWin<G, PPL, 
     if (job) {  // the deferred residue rides along as a sixth chain
 #pragma unroll
       for (int k = 0; k < PPL; ++k) prod[5][k] = rdif[0][k];
-      sums_g<G, 6, PPL, PATCH, WIN, EXACT>(w, prod, red, a.red_pitch, npx, lane, S);
+      sums<6, PPL, PATCH, WIN, EXACT>(w, prod, red, a.red_pitch, npx, lane, S);
       verdict(S[5]);
       stepped = step && act;
     } else {
       float (&p5)[5][PPL] = *reinterpret_cast<float (*)[5][PPL]>(&prod);
       float (&s5)[5] = *reinterpret_cast<float (*)[5]>(&S);
-      sums_g<G, 5, PPL, PATCH, WIN, EXACT>(w, p5, red, a.red_pitch, npx, lane, s5);
+      sums<5, PPL, PATCH, WIN, EXACT>(w, p5, red, a.red_pitch, npx, lane, s5);
     }
     PROF_ADD(1, t_s0);
     PROF_T(t_v0);
@@ -669,11 +651,11 @@ __device__ int track_level_g(PROF_DECL const TrkArgs &a, const GroupWin<G, PPL, 
         status = kSmallDet;  // x2 has not moved: the post-loop window test repeats this iteration's
         act = false;
       } else {
-        const float dx = uni<G>((gyy * ex - gxy * ey) / det);
-        const float dy = uni<G>((gxx * ey - gxy * ex) / det);
+        const float dx = uni((gyy * ex - gxy * ey) / det);
+        const float dy = uni((gxx * ey - gxy * ex) / det);
         status = kTracked;
-        x2 = uni<G>(x2 + dx);
-        y2 = uni<G>(y2 + dy);
+        x2 = uni(x2 + dx);
+        y2 = uni(y2 + dy);
         ++it;
         if (!((fabsf(dx) >= a.min_disp || fabsf(dy) >= a.min_disp) && it < a.max_it)) fin = true;
       }
@@ -690,14 +672,12 @@ __device__ int track_level_g(PROF_DECL const TrkArgs &a, const GroupWin<G, PPL, 
   return kTracked;
 }
 
-// one frame of KLTTrackFeatures for the feature of this lane's group (:1348-1437)
-template <int G, int PPL, bool PATCH, int WIN, bool EXACT, bool LI, bool BAND, class LevA, class LevB>
-__device__ __forceinline__ void track_feature_g(PROF_DECL const TrkArgs &a, const GroupWin<G, PPL, PATCH, WIN> &w,
-                                                LevA LA,
-                                                LevB LB,
-                                                float &fx, float &fy, int &fv, bool live, int lane,
-                                                float *red, ResCarry<PPL> &rc, bool job, bool defer,
-                                                const TrkLevel &R, int &rstat, TrkCount &cnt) {
+// one frame of KLTTrackFeatures for the wave's feature (:1348-1437)
+template <int PPL, bool PATCH, int WIN, bool EXACT, bool LI, bool BAND, class LevA, class LevB>
+__device__ __forceinline__ void track_feature(PROF_DECL const TrkArgs &a, const LaneWin<PPL, PATCH, WIN> &w,
+                                              LevA LA, LevB LB, float &fx, float &fy, int &fv, bool live, int lane,
+                                              float *red, ResCarry<PPL> &rc, bool job, bool defer,
+                                              const TrkLevel &R, int &rstat, TrkCount &cnt) {
   // job: the previous frame's residue is pending (rc) and resolves in the
   // coarsest level's first pass; if it loses that frame's feature this frame
   // is not tracked and fx/fy/fv stay as they are (the caller records the
@@ -706,8 +686,8 @@ __device__ __forceinline__ void track_feature_g(PROF_DECL const TrkArgs &a, cons
   for (int r = a.nlev - 1; r >= 0; --r) {
     // xloc /= subsampling (trackFeatures.c:1353): a power of two divides
     // exactly, so the reciprocal's product is the same float
-    xl = uni<G>(a.ss_inv != 0.0f ? xl * a.ss_inv : xl / a.ss);
-    yl = uni<G>(a.ss_inv != 0.0f ? yl * a.ss_inv : yl / a.ss);
+    xl = uni(a.ss_inv != 0.0f ? xl * a.ss_inv : xl / a.ss);
+    yl = uni(a.ss_inv != 0.0f ? yl * a.ss_inv : yl / a.ss);
   }
   float xo = xl, yo = yl;
   int val = kTracked;
@@ -715,16 +695,15 @@ __device__ __forceinline__ void track_feature_g(PROF_DECL const TrkArgs &a, cons
   for (int r = a.nlev - 1; r >= 0; --r) {
     if (!wave_any(go)) break;
     if (go) {  // a feature that stopped keeps the coordinates of its last level (border test below)
-      xl = uni<G>(xl * a.ss);
-      yl = uni<G>(yl * a.ss);
-      xo = uni<G>(xo * a.ss);
-      yo = uni<G>(yo * a.ss);
+      xl = uni(xl * a.ss);
+      yl = uni(yl * a.ss);
+      xo = uni(xo * a.ss);
+      yo = uni(yo * a.ss);
     }
     const bool lj = job && r == a.nlev - 1;
     PROF_T(t_l0);
-    const int v = track_level_g<G, PPL, PATCH, WIN, EXACT, LI, BAND>(PROF_ARG a, w, LA(r), LB(r), xl, yl, xo, yo, go,
-                                                               lane, red, r == 0, rc, lj, defer && r == 0, R,
-                                                               rstat, cnt);
+    const int v = track_level<PPL, PATCH, WIN, EXACT, LI, BAND>(PROF_ARG a, w, LA(r), LB(r), xl, yl, xo, yo, go, lane,
+                                                                red, r == 0, rc, lj, defer && r == 0, R, rstat, cnt);
     PROF_ADD(10, t_l0);
     if (lj && rstat != kTracked) return;
     if (go) {
@@ -760,11 +739,10 @@ __device__ __forceinline__ void track_feature_g(PROF_DECL const TrkArgs &a, cons
 // result.  The residue is not deferred (frame j's status comes first), and
 // every level call starts with an empty patch cache.
 // The body is track_body.h, shared by the two kernels below.
-template <int G, int PPL, bool PATCH, int WIN, bool EXACT, bool LI, bool BAND>
+template <int PPL, bool PATCH, int WIN, bool EXACT, bool LI, bool BAND>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KLT_TRACK_WAVES))) void k_track_frames_g(TrkArgs a, TrkFramesArgs b, float *__restrict__ fx,
                                                            float *__restrict__ fy, int *__restrict__ fv, int n) {
-  constexpr int LG = kWave / G;
-  __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][6 * G * (LG * PPL + 4) + 16];
+  __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][red_floats(PPL)];
   constexpr bool FB = false, AFF = false;
   const TrkFbArgs fb{};
   const TrkAffArgs af{};
@@ -772,12 +750,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KLT_TRAC
 #include "track_body.h"
 }
 
-template <int G, int PPL, bool PATCH, int WIN, bool LI>
+template <int PPL, bool PATCH, int WIN, bool LI>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KLT_TRACK_WAVES))) void k_track_frames_g_fb(
     TrkArgs a, TrkFramesArgs b, TrkFbArgs fb, float *__restrict__ fx, float *__restrict__ fy, int *__restrict__ fv,
     int n) {
-  constexpr int LG = kWave / G;
-  __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][6 * G * (LG * PPL + 4) + 16];
+  __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][red_floats(PPL)];
   constexpr bool EXACT = true, BAND = false, FB = true, AFF = false;
   const TrkAffArgs af{};
   float *const aff_dyn = nullptr;
@@ -790,12 +767,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(KLT_TRAC
 // or it is re-tracked from the stored window and rejected when that fails.
 // Exact sums, whole-frame pyramids, level 0 as planes, the residue in place.
 // The stage's ordered-sum staging is dynamic LDS sized for the mode.
-template <int G, int PPL, bool PATCH, int WIN, bool LI>
+template <int PPL, bool PATCH, int WIN, bool LI>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPL == 1 ? KLT_AFF_WAVES : 1))) void k_track_frames_g_aff(
     TrkArgs a, TrkFramesArgs b, TrkAffArgs af, float *__restrict__ fx, float *__restrict__ fy, int *__restrict__ fv,
     int n) {
-  constexpr int LG = kWave / G;
-  __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][6 * G * (LG * PPL + 4) + 16];
+  __shared__ __attribute__((aligned(16))) float red_all[kBlock / kWave][red_floats(PPL)];
   extern __shared__ __attribute__((aligned(16))) float aff_dyn[];
   constexpr bool EXACT = true, BAND = false, FB = false, AFF = true;
   const TrkFbArgs fb{};
@@ -909,75 +885,63 @@ __global__ __launch_bounds__(kSortThreads) void k_band_order(const float *__rest
   }
 }
 
-template <int G, int PPL, bool PATCH, int WIN, bool EXACT, bool LI, bool BAND = true>
-void launch_g(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y, int *v, int n) {
-  const int per = (kBlock / kWave) * G;  // features per workgroup
+// The instance for a window: f(PPL, PATCH, WIN), each an integral constant
+template <class F>
+void with_instance(bool patch, bool win7, int npx, F f) {
+  using std::integral_constant;
+  constexpr integral_constant<int, 1> one{};
+  constexpr integral_constant<int, 0> any{};  // WIN = 0: the window's size is a run-time value
+  constexpr integral_constant<int, 7> seven{};
+  if (patch && win7) f(one, std::true_type{}, seven);
+  else if (patch) f(one, std::true_type{}, any);
+  else if (win7) f(one, std::false_type{}, seven);
+  else if (npx <= kWave) f(one, std::false_type{}, any);
+  else if (npx <= 4 * kWave) f(integral_constant<int, 4>{}, std::false_type{}, any);
+  else f(integral_constant<int, 16>{}, std::false_type{}, any);
+}
+
+// One wave per feature: the grid for n features (or 8 XCD runs), and the launch
+template <class K, class... Args>
+void launch_waves(K kernel, size_t lds, hipStream_t st, int xcd_per, int n, Args... args) {
+  const int per = kBlock / kWave;  // features per workgroup
   const int nb = (n + per - 1) / per;
-  const int grid = b.xcd_per > 0 ? 8 * b.xcd_per : nb;
-  hipLaunchKernelGGL((k_track_frames_g<G, PPL, PATCH, WIN, EXACT, LI, BAND>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y,
-                     v, n);
+  const int grid = xcd_per > 0 ? 8 * xcd_per : nb;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, st, args...);
 }
 
 template <bool EXACT, bool LI>
-void launch_sel(bool patch, bool win7, int npx, hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, float *x,
-                float *y, int *v, int n) {
-  // the default configuration has an instance without the band checks (its
-  // escape test and the spilled scalar registers it costs: -1.5..3 % per frame)
-  if (patch && win7 && !a.escape) launch_g<1, 1, true, 7, EXACT, LI, false>(st, a, b, x, y, v, n);
-  else if (patch && win7) launch_g<1, 1, true, 7, EXACT, LI>(st, a, b, x, y, v, n);
-  else if (patch) launch_g<1, 1, true, 0, EXACT, LI>(st, a, b, x, y, v, n);
-  else if (win7) launch_g<1, 1, false, 7, EXACT, LI>(st, a, b, x, y, v, n);
-  else if (npx <= kWave) launch_g<1, 1, false, 0, EXACT, LI>(st, a, b, x, y, v, n);
-  else if (npx <= 4 * kWave) launch_g<1, 4, false, 0, EXACT, LI>(st, a, b, x, y, v, n);
-  else launch_g<1, 16, false, 0, EXACT, LI>(st, a, b, x, y, v, n);
+void launch_plain(bool patch, bool win7, int npx, hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, float *x,
+                  float *y, int *v, int n) {
+  with_instance(patch, win7, npx, [&](auto ppl, auto pat, auto win) {
+    // the default configuration has an instance without the band checks (its
+    // escape test and the spilled scalar registers it costs: -1.5..3 % per frame)
+    if constexpr (pat && win == 7) {
+      if (!a.escape)
+        return launch_waves(k_track_frames_g<ppl, pat, win, EXACT, LI, false>, 0, st, b.xcd_per, n, a, b, x, y, v, n);
+    }
+    launch_waves(k_track_frames_g<ppl, pat, win, EXACT, LI, true>, 0, st, b.xcd_per, n, a, b, x, y, v, n);
+  });
 }
 
-template <int G, int PPL, bool PATCH, int WIN, bool LI>
-void launch_g_fb(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkFbArgs &fb, float *x, float *y,
-                 int *v, int n) {
-  const int per = (kBlock / kWave) * G;
-  const int nb = (n + per - 1) / per;
-  const int grid = b.xcd_per > 0 ? 8 * b.xcd_per : nb;
-  hipLaunchKernelGGL((k_track_frames_g_fb<G, PPL, PATCH, WIN, LI>), dim3(grid), dim3(kBlock), 0, st, a, b, fb, x, y, v,
-                     n);
-}
-
-// launch_sel's choice of instance, for the forward-backward kernels
 template <bool LI>
-void launch_sel_fb(bool patch, bool win7, int npx, hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b,
-                   const TrkFbArgs &fb, float *x, float *y, int *v, int n) {
-  if (patch && win7) launch_g_fb<1, 1, true, 7, LI>(st, a, b, fb, x, y, v, n);
-  else if (patch) launch_g_fb<1, 1, true, 0, LI>(st, a, b, fb, x, y, v, n);
-  else if (win7) launch_g_fb<1, 1, false, 7, LI>(st, a, b, fb, x, y, v, n);
-  else if (npx <= kWave) launch_g_fb<1, 1, false, 0, LI>(st, a, b, fb, x, y, v, n);
-  else if (npx <= 4 * kWave) launch_g_fb<1, 4, false, 0, LI>(st, a, b, fb, x, y, v, n);
-  else launch_g_fb<1, 16, false, 0, LI>(st, a, b, fb, x, y, v, n);
+void launch_fb(bool patch, bool win7, int npx, hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b,
+               const TrkFbArgs &fb, float *x, float *y, int *v, int n) {
+  with_instance(patch, win7, npx, [&](auto ppl, auto pat, auto win) {
+    launch_waves(k_track_frames_g_fb<ppl, pat, win, LI>, 0, st, b.xcd_per, n, a, b, fb, x, y, v, n);
+  });
 }
 
-template <int G, int PPL, bool PATCH, int WIN, bool LI>
-void launch_g_aff(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkAffArgs &af, float *x, float *y,
-                  int *v, int n) {
-  const int per = (kBlock / kWave) * G;
-  const int nb = (n + per - 1) / per;
-  const int grid = b.xcd_per > 0 ? 8 * b.xcd_per : nb;
-  const size_t lds = sizeof(float) * (kBlock / kWave) * (size_t)af.lds_wave;
-  if (lds > (48u << 10))  // a larger KLT_AFF_CH: past the default dynamic allowance
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_track_frames_g_aff<G, PPL, PATCH, WIN, LI>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((k_track_frames_g_aff<G, PPL, PATCH, WIN, LI>), dim3(grid), dim3(kBlock), lds, st, a, b, af, x, y,
-                     v, n);
-}
-
-// launch_sel's choice of instance, for the affine-check kernels
 template <bool LI>
-void launch_sel_aff(bool patch, bool win7, int npx, hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b,
-                    const TrkAffArgs &af, float *x, float *y, int *v, int n) {
-  if (patch && win7) launch_g_aff<1, 1, true, 7, LI>(st, a, b, af, x, y, v, n);
-  else if (patch) launch_g_aff<1, 1, true, 0, LI>(st, a, b, af, x, y, v, n);
-  else if (win7) launch_g_aff<1, 1, false, 7, LI>(st, a, b, af, x, y, v, n);
-  else if (npx <= kWave) launch_g_aff<1, 1, false, 0, LI>(st, a, b, af, x, y, v, n);
-  else if (npx <= 4 * kWave) launch_g_aff<1, 4, false, 0, LI>(st, a, b, af, x, y, v, n);
-  else launch_g_aff<1, 16, false, 0, LI>(st, a, b, af, x, y, v, n);
+void launch_aff(bool patch, bool win7, int npx, hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b,
+                const TrkAffArgs &af, float *x, float *y, int *v, int n) {
+  with_instance(patch, win7, npx, [&](auto ppl, auto pat, auto win) {
+    const auto kernel = k_track_frames_g_aff<ppl, pat, win, LI>;
+    const size_t lds = sizeof(float) * (kBlock / kWave) * (size_t)af.lds_wave;
+    if (lds > (48u << 10))  // a larger KLT_AFF_CH: past the default dynamic allowance
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds);
+    launch_waves(kernel, lds, st, b.xcd_per, n, a, b, af, x, y, v, n);
+  });
 }
 
 }  // namespace
@@ -991,22 +955,22 @@ hipError_t launch_track_frames(hipStream_t st, bool exact, bool li, bool patch, 
                                const TrkFbArgs *fb, const TrkAffArgs *af) {
   if (af) {  // the runtime refuses band calls, fast sums and the forward-backward check with it on
     if (!exact || a.escape || fb) return hipErrorInvalidValue;
-    if (li) launch_sel_aff<true>(patch, win7, npx, st, a, b, *af, x, y, v, n);
-    else launch_sel_aff<false>(patch, win7, npx, st, a, b, *af, x, y, v, n);
+    if (li) launch_aff<true>(patch, win7, npx, st, a, b, *af, x, y, v, n);
+    else launch_aff<false>(patch, win7, npx, st, a, b, *af, x, y, v, n);
     return hipGetLastError();
   }
   if (fb) {  // the runtime refuses band calls and fast sums with the check on
     if (!exact || a.escape) return hipErrorInvalidValue;
-    if (li) launch_sel_fb<true>(patch, win7, npx, st, a, b, *fb, x, y, v, n);
-    else launch_sel_fb<false>(patch, win7, npx, st, a, b, *fb, x, y, v, n);
+    if (li) launch_fb<true>(patch, win7, npx, st, a, b, *fb, x, y, v, n);
+    else launch_fb<false>(patch, win7, npx, st, a, b, *fb, x, y, v, n);
     return hipGetLastError();
   }
   if (exact) {
-    if (li) launch_sel<true, true>(patch, win7, npx, st, a, b, x, y, v, n);
-    else launch_sel<true, false>(patch, win7, npx, st, a, b, x, y, v, n);
+    if (li) launch_plain<true, true>(patch, win7, npx, st, a, b, x, y, v, n);
+    else launch_plain<true, false>(patch, win7, npx, st, a, b, x, y, v, n);
   } else {
-    if (li) launch_sel<false, true>(patch, win7, npx, st, a, b, x, y, v, n);
-    else launch_sel<false, false>(patch, win7, npx, st, a, b, x, y, v, n);
+    if (li) launch_plain<false, true>(patch, win7, npx, st, a, b, x, y, v, n);
+    else launch_plain<false, false>(patch, win7, npx, st, a, b, x, y, v, n);
   }
   return hipGetLastError();
 }

@@ -2,7 +2,7 @@
 // k_track_frames_g_aff (track.hip), included inside each kernel: the plain
 // kernels keep their by-value arguments and compile to what they were before
 // the forward-backward and affine instances existed.  The including kernel
-// provides: the template parameters G, PPL, PATCH, WIN, EXACT, LI, BAND;
+// provides: the template parameters PPL, PATCH, WIN, EXACT, LI, BAND;
 // constexpr bool FB, AFF; TrkArgs a; TrkFramesArgs b; TrkFbArgs fb; TrkAffArgs
 // af; fx, fy, fv, n; the LDS array red_all; and, AFF, the dynamic LDS aff_dyn.
   if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
@@ -13,30 +13,21 @@
   // band mode: the grid is sized for every feature, but only the n_dev kept
   // ones are processed -- spread THEIR blocks over the 8 XCDs (a per-XCD run
   // sized for all features would put a small band on one XCD)
-  const int xcd_per = b.n_dev && b.xcd_per > 0 ? ((n + kBlock / kWave * G - 1) / (kBlock / kWave * G) + 7) / 8
-                                                 : b.xcd_per;
+  const int xcd_per = b.n_dev && b.xcd_per > 0 ? ((n + kBlock / kWave - 1) / (kBlock / kWave) + 7) / 8 : b.xcd_per;
   if (xcd_per > 0 && (int)(blockIdx.x / 8) >= xcd_per) return;  // past this XCD's run: no duplicate slots
   const int blk = xcd_per > 0 ? (int)(blockIdx.x % 8) * xcd_per + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-  const int s0 = (blk * (kBlock / kWave) + wave) * G;
-  if (s0 >= n) return;  // whole wave; the kernel has no workgroup barrier
-  const int g = lane / LG, slot = s0 + g;
-  const bool exists = slot < n;
-  const int f = exists ? (b.perm ? b.perm[slot] : slot) : 0;
-  float x = 0.0f, y = 0.0f;
-  int v = -1;
-  if (exists) {
-    x = uni<G>(fx[f]);
-    y = uni<G>(fy[f]);
-    v = uni<G>(fv[f]);
-  }
-  const GroupWin<G, PPL, PATCH, WIN> w = group_window<G, PPL, PATCH, WIN>(a.ww, a.wh, lane);
+  const int slot = blk * (kBlock / kWave) + wave;
+  if (slot >= n) return;  // whole wave; the kernel has no workgroup barrier
+  const int f = b.perm ? b.perm[slot] : slot;
+  float x = uni(fx[f]), y = uni(fy[f]);
+  int v = uni(fv[f]);
+  const LaneWin<PPL, PATCH, WIN> w = lane_window<PPL, PATCH, WIN>(a.ww, a.wh, lane);
   {  // row pads of the ordered-sum staging stay +0 for the whole kernel
     float *red = red_all[wave];
-    constexpr int RED = 6 * G * (LG * PPL + 4) + 16;
-    for (int i = lane; i < RED; i += kWave) red[i] = 0.0f;
+    for (int i = lane; i < red_floats(PPL); i += kWave) red[i] = 0.0f;
     lds_wave_sync();
   }
-  const bool head = exists && (lane % LG) == 0;
+  const bool head = lane == 0;
 #ifdef KLT_TRACK_PROF
   Prof prof;
   const unsigned long long wall0 = wall_clock64();
@@ -44,7 +35,7 @@
   // deferred residues (ResCarry): one-feature waves, exact sums, default gain
   // (band mode too: the residue's rows were checked against the band at frame
   // j's final position, and an escape voids the whole chunk anyway)
-  const bool merge = !FB && !AFF && G == 1 && EXACT && !LI && a.merge_res && a.nlev >= 2;
+  const bool merge = !FB && !AFF && EXACT && !LI && a.merge_res && a.nlev >= 2;
   ResCarry<PPL> rc;
   TrkCount cnt;
   // affine check: the feature's six values and its window state stay in
@@ -52,23 +43,20 @@
   float aff6[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   int ast = 0;
   if constexpr (AFF) {
-    static_assert(G == 1, "the affine stage is wave-uniform: one feature per wave");
-    if (exists) {
 #pragma unroll
-      for (int q = 0; q < 6; ++q) aff6[q] = uni<G>(af.aff[6 * (long)f + q]);
-      ast = uni<G>(af.state[f]);
-      if (af.fresh) ast = ast != 0 ? 1 : 0;  // held from before the call
-    }
+    for (int q = 0; q < 6; ++q) aff6[q] = uni(af.aff[6 * (long)f + q]);
+    ast = uni(af.state[f]);
+    if (af.fresh) ast = ast != 0 ? 1 : 0;  // held from before the call
   }
   for (int j = 0; j < b.nframes; ++j) {
     const bool job = rc.pending;  // frame j-1 is tentatively tracked at (x, y)
-    const bool live = exists && (v >= 0 || job);  // lost features are not tracked (:1346)
+    const bool live = v >= 0 || job;  // lost features are not tracked (:1346)
     const float xp = x, yp = y;
     int rstat = kTracked;
     PROF_T(t_f0);
     if (wave_any(live)) {
       auto LA = [&](int r) { return j == 0 ? a.A[r] : at_frame(a.B[r], (long)(j - 1) * b.lfs[r]); };
-      track_feature_g<G, PPL, PATCH, WIN, EXACT, LI, BAND>(
+      track_feature<PPL, PATCH, WIN, EXACT, LI, BAND>(
           PROF_ARG a, w, LA, [&](int r) { return at_frame(a.B[r], (long)j * b.lfs[r]); }, x, y, v, live, lane,
           red_all[wave], rc, job, merge && j + 1 < b.nframes, LA(0), rstat, cnt);
     }
@@ -79,7 +67,7 @@
         auto LA = [&](int r) { return j == 0 ? a.A[r] : at_frame(a.B[r], (long)(j - 1) * b.lfs[r]); };
         float xb = x, yb = y;
         int vb = v;
-        track_feature_g<G, PPL, PATCH, WIN, EXACT, LI, BAND>(
+        track_feature<PPL, PATCH, WIN, EXACT, LI, BAND>(
             PROF_ARG a, w, [&](int r) { return at_frame(a.B[r], (long)j * b.lfs[r]); }, LA, xb, yb, vb, back, lane,
             red_all[wave], rc, false, false, LA(0), rstat, cnt);
         if (back) {
@@ -87,7 +75,7 @@
           if (!rej) {  // five float operations, each rounded (contraction is off in this file)
             const float dx = xb - xp, dy = yb - yp;
             const float dx2 = dx * dx, dy2 = dy * dy;
-            e = uni<G>(dx2 + dy2);
+            e = uni(dx2 + dy2);
             rej = e > fb.t2;
           }
           if (rej) {
@@ -103,41 +91,39 @@
       // the reference's record stage (trackFeatures.c:1438-1497) for a feature
       // frame j's translation step left TRACKED (no deferred residue: its
       // verdict is final), on level 0 as planes; every operand is wave-uniform
-      if (exists) {
-        if (live && v == kTracked) {
-          const TrkLevel P = j == 0 ? a.A[0] : at_frame(a.B[0], (long)(j - 1) * b.lfs[0]);
-          const TrkLevel Q = at_frame(a.B[0], (long)j * b.lfs[0]);
-          const AffImg I1{P.img, P.gx, P.gy, P.w, P.h}, I2{Q.img, Q.gx, Q.gy, Q.w, Q.h};
-          const int S = (af.p.ww + 2) * (af.p.wh + 2);
-          float *lds = aff_dyn + wave * af.lds_wave;
-          const int was = ast;
-          int status;
-          ast = aff_stage<kAffChunk>(lds, lds + af.lds_wave - aff::SOLVE, af.p, I1, I2,
-                                     af.store + (size_t)f * 3 * S, aff6, xp, yp, x, y, ast, lane, status);
-          if (status != kTracked) {
-            x = -1.0f;
-            y = -1.0f;
-            v = status;
-          }
-          if (was == 0) {
-            // the window this wave just stored is read from the next frame on,
-            // each lane reading what other lanes wrote (and lines that hold a
-            // neighbour's window too): stores complete, stale lines dropped
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          }
-        } else {
-          ast = 0;  // lost by the translation step, now or before: no window
+      if (live && v == kTracked) {
+        const TrkLevel P = j == 0 ? a.A[0] : at_frame(a.B[0], (long)(j - 1) * b.lfs[0]);
+        const TrkLevel Q = at_frame(a.B[0], (long)j * b.lfs[0]);
+        const AffImg I1{P.img, P.gx, P.gy, P.w, P.h}, I2{Q.img, Q.gx, Q.gy, Q.w, Q.h};
+        const int S = (af.p.ww + 2) * (af.p.wh + 2);
+        float *lds = aff_dyn + wave * af.lds_wave;
+        const int was = ast;
+        int status;
+        ast = aff_stage<kAffChunk>(lds, lds + af.lds_wave - aff::SOLVE, af.p, I1, I2,
+                                   af.store + (size_t)f * 3 * S, aff6, xp, yp, x, y, ast, lane, status);
+        if (status != kTracked) {
+          x = -1.0f;
+          y = -1.0f;
+          v = status;
         }
-        if (head) {
-          if (af.tab_aff) {
-            float *row = af.tab_aff + 6 * ((long)j * af.stride + f);
+        if (was == 0) {
+          // the window this wave just stored is read from the next frame on,
+          // each lane reading what other lanes wrote (and lines that hold a
+          // neighbour's window too): stores complete, stale lines dropped
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        }
+      } else {
+        ast = 0;  // lost by the translation step, now or before: no window
+      }
+      if (head) {
+        if (af.tab_aff) {
+          float *row = af.tab_aff + 6 * ((long)j * af.stride + f);
 #pragma unroll
-            for (int q = 0; q < 6; ++q) row[q] = aff6[q];
-          }
-          if (af.tab_state) af.tab_state[(long)j * af.stride + f] = ast;
+          for (int q = 0; q < 6; ++q) row[q] = aff6[q];
         }
+        if (af.tab_state) af.tab_state[(long)j * af.stride + f] = ast;
       }
     }
     PROF_ADD(4, t_f0);
