@@ -61,6 +61,26 @@ int klt_amd_set_fb_check(KLT_TrackingContext tc, int on, float max_dist);
 void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int nframes, int ncols, int nrows,
                       KLT_FeatureList fl, KLT_FeatureTable ft, int ft_col);
 
+/* KLTTrackSequence for nseq independent sequences of one geometry (a stereo
+   rig, a camera array, many clips) in one call:
+     for (s = 0; s < nseq; s++)
+       KLTTrackSequence(tc_s, frames[s], nframes, ncols, nrows, fl[s], ft ? ft[s] : NULL, ft_col);
+   on nseq fresh copies tc_s of tc (its parameters and settings, no kept
+   pyramid), with bit-identical lists and tables.  tc's own kept pyramid
+   (sequential mode) is neither read nor changed.  The sequences are tracked
+   together, one device launch per 16 frames serving all of them
+   (klt_hip_track_frames_multi): frames go up group by group through pinned
+   staging, the upload is not overlapped with the device work.  Where that
+   call does not apply -- KLTTrackSequence itself would fall back to its loop
+   (a kernel-cache corner case, internal images), the affine or the
+   forward-backward check is on, more than KLT_HIP_MAX_SEQUENCES sequences, or
+   a configuration the call refuses (another window, lighting-insensitive
+   mode, fast sums, other pyramid parameters) -- it runs exactly the loop
+   above, each sequence on a context of its own.  Argument checks are
+   KLTTrackSequence's, per sequence; ft may be NULL, and so may any ft[s]. */
+void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, int nseq, int nframes, int ncols, int nrows,
+                       KLT_FeatureList *fl, KLT_FeatureTable *ft, int ft_col);
+
 /* host side of the synthetic generator (include/klt_synth.h) */
 void klt_synth_frame(uint64_t seed, int t, int ncols, int nrows, unsigned char *out);
 /* the reference quicksort's permutation on {val, idx} pairs (test hook) */

@@ -413,6 +413,57 @@ int klt_hip_frames_begin_slot(klt_hip_ctx *ctx, int slot);
    last tracked frame's) into pyramid slot `slot` (device-to-device) */
 int klt_hip_frames_end_slot(klt_hip_ctx *ctx, int slot);
 
+/* nseq independent sequences of the same geometry and parameters in one
+   batched call: one pair of pyramid launches and one tracker launch per chunk
+   serve all of them (a feature's wave walks its chunk alone, so a launch of
+   few features leaves most of the device idle; the sequences fill it).
+   Sequence s has nframes + 1 device frames at frames + s*seq_stride + f*stride:
+   f = 0 is the image its list starts on, f = 1..nframes are tracked.  n_seq
+   (host int[nseq]) gives its feature count, 0 allowed; x/y/val (device, updated
+   in place) hold the lists one after the other, sequence 0 first (n = the sum
+   of n_seq).  tab_* (device, optional: all three or NULL) row j (tab_stride >=
+   n apart) receives all nseq lists after tracked frame j, in that order.
+   The result is, byte for byte, what klt_hip_frames_begin on frame 0 followed
+   by klt_hip_track_frames on frames 1..nframes gives for each sequence on its
+   own; it does not depend on chunk, on the bank budget or on the tuning hooks.
+   Asynchronous, on the context's stream alone: klt_hip_set_frames_overlap's
+   schedules are ignored (each chunk's pyramids, then its tracker), and so is
+   klt_hip_set_track_order (features are processed in input order, which is
+   one image per run of workgroups already).
+   Banks: frame-major, frame j of every sequence adjacent, each bank nseq*chunk
+   pyramids; the nseq pyramids a chunk starts from are the previous bank's last
+   group, for the first chunk a group of their own in the bank that the third
+   chunk reuses.  Level 0
+   is kept as full records ({gx, gy, img} per pixel); klt_hip_set_lazy_grad does
+   not apply to this call.  Pyramids are built by one pair of launches per chunk
+   when stride == nseq*seq_stride (frame-major frames), else by one pair per
+   sequence.  A bank budget too small for the requested chunk gives the largest
+   chunk that fits (klt_hip_frames_chunk reports it); the call fails cleanly
+   when not even one group of nseq pyramids per bank fits.
+   The kept pyramid: the call carries its own start images and does not read
+   the pyramid kept by klt_hip_frames_begin* or an earlier call; afterwards the
+   context has no current pyramid, as after klt_hip_ctx_reset -- a later plain
+   klt_hip_track_frames* call needs klt_hip_frames_begin* first.  (The nseq last
+   pyramids are not carried into a next multi call either: that call builds its
+   start images again.)
+   Covered: the default configuration -- fused pyramids (klt_hip_fused_path),
+   7x7 window, KLT_HIP_EXACT sums, tracked by k_track7.  Refused with -1 and a
+   message before any launch, x/y/val untouched (klt_hip_multi_covers asks
+   beforehand: 1 covered, 0 refused with the message set): the forward-backward
+   check (klt_hip_set_fb), the affine check (klt_hip_set_frames_affine),
+   KLT_HIP_FAST sums, any other window, lighting-insensitive mode, the generic
+   pyramid path (other pyramid parameters, klt_hip_set_path), the generic
+   tracker (klt_hip_set_track_impl 1, klt_hip_set_track_patch 0, klt_hip_set_prof);
+   nseq < 1 or > KLT_HIP_MAX_SEQUENCES, a negative n_seq[s], nframes < 0,
+   chunk < 1, pitch < ncols, one or two of the three table arrays,
+   tab_stride < n. */
+#define KLT_HIP_MAX_SEQUENCES 64
+int klt_hip_multi_covers(klt_hip_ctx *ctx, const klt_hip_pyr_desc *pdesc, const klt_hip_track_desc *tdesc);
+int klt_hip_track_frames_multi(klt_hip_ctx *ctx, const klt_hip_pyr_desc *pdesc, const klt_hip_track_desc *tdesc,
+                               const unsigned char *frames, long pitch, long stride, long seq_stride, int nseq,
+                               int nframes, int chunk, const int *n_seq, float *x, float *y, int *val, float *tab_x,
+                               float *tab_y, int *tab_val, long tab_stride);
+
 /* feature-table rows handed back by klt_hip_track_frames_host: tracked frames
    frame0 .. frame0+nframes-1 (row j at x + j*stride), features [f0, f1).
    Called from several threads at once, on disjoint feature ranges. */

@@ -1154,6 +1154,210 @@ EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int
 }
 
 /* ------------------------------------------------------------------ */
+/* KLTTrackSequences: KLTTrackSequence for nseq independent sequences of */
+/* one geometry, each on a fresh copy of tc, through one batched device  */
+/* call per group of frames (klt_hip_track_frames_multi).  Bit-identical */
+/* to that loop; runs the loop itself where the multi call does not apply.*/
+/* ------------------------------------------------------------------ */
+/* a tracking context with tc's parameters and settings and no kept pyramid */
+static KLT_TrackingContext fresh_copy(KLT_TrackingContext tc)
+{
+  KLT_TrackingContext t = KLTCreateTrackingContext();
+  klt_ctx_full *g = FULL(t);
+  g->pub = *tc;
+  t->pyramid_last = t->pyramid_last_gradx = t->pyramid_last_grady = NULL;
+  g->reduction = FULL(tc)->reduction;
+  g->fb_on = FULL(tc)->fb_on;
+  g->fb_dist = FULL(tc)->fb_dist;
+  return t;
+}
+
+#define MULTI_STAGE_BYTES ((size_t)256 << 20) /* pinned staging of one group of frames, at most */
+enum { MEMCPY_H2D = 1, MEMCPY_D2H = 2 };      /* klt_hip_memcpy's kinds (hipMemcpyKind) */
+
+EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, int nseq, int nframes, int ncols,
+                              int nrows, KLT_FeatureList *fl, KLT_FeatureTable *ft, int ft_col)
+{
+  klt_ctx_full *f = FULL(tc);
+  klt_hip_ctx *dev = NULL;
+  klt_hip_pyr_desc D, d1, d2, e1, e2;
+  klt_hip_track_desc td;
+  taps_state st, after1;
+  const int T = nframes - 1;
+  int s, k, j, j0, n = 0, F, multi, any_ft = 0, pinned;
+  int *counts, *hv, *tv = NULL;
+  float *hx, *hy, *tx = NULL, *ty = NULL;
+  unsigned char *stage, *dfr;
+  float *dx, *dy, *dtx = NULL, *dty = NULL;
+  int *dv, *dtv = NULL;
+  size_t fb, stage_bytes;
+
+  if (nseq < 1 || nframes < 2) return;
+  window_fix(tc, NULL);
+  affine_check_tc(tc);
+  for (s = 0; s < nseq; s++) {
+    KLT_FeatureTable t = ft ? ft[s] : NULL;
+    if (t && (ft_col < 0 || ft_col + T > t->nFrames))
+      KLTError("(KLTStoreFeatures) Frame number %d is not between 0 and %d", ft_col < 0 ? ft_col : ft_col + T - 1,
+               t->nFrames - 1);
+    if (t && t->nFeatures != fl[s]->nFeatures)
+      KLTError("(KLTStoreFeatures) FeatureList and FeatureTable must have the same number of features");
+    if (t) any_ft = 1;
+    n += fl[s]->nFeatures;
+  }
+
+  /* the multi call applies when every sequence's KLTTrackSequence would take
+     its batched path from its own frames[0] with one and the same pyramid
+     description: the dry run of its kernel-cache lookups, sequence after
+     sequence as the loop would make them */
+  multi = nseq <= KLT_HIP_MAX_SEQUENCES && tc->affineConsistencyCheck < 0 && !f->fb_on && !tc->writeInternalImages;
+  pthread_mutex_lock(&g_taps_lock);
+  st = g_taps;
+  pthread_mutex_unlock(&g_taps_lock);
+  memset(&D, 0, sizeof D);
+  for (s = 0; multi && s < nseq; s++) {
+    pyr_desc_in(&st, tc, ncols, nrows, tc->nPyramidLevels, 1, &d1);
+    pyr_desc_in(&st, tc, ncols, nrows, tc->nPyramidLevels, 1, &d2);
+    after1 = st;
+    if (!tc->sequentialMode) pyr_desc_in(&st, tc, ncols, nrows, tc->nPyramidLevels, 1, &e1);
+    pyr_desc_in(&st, tc, ncols, nrows, tc->nPyramidLevels, 1, &e2);
+    if (s == 0) D = d2;
+    multi = taps_state_eq(&st, &after1) && !memcmp(&e2, &d2, sizeof d2) &&
+            (tc->sequentialMode || !memcmp(&e1, &d2, sizeof d2)) && !memcmp(&d1, &d2, sizeof d2) &&
+            !memcmp(&d2, &D, sizeof D);
+  }
+  if (multi) {
+    dev = device_of(tc);
+    apply_fb(tc, "KLTTrackSequences");
+    klt_amd_track_desc(tc, &td);
+    multi = klt_hip_multi_covers(dev, &D, &td) == 1;
+  }
+  if (!multi) {
+    for (s = 0; s < nseq; s++) {
+      KLT_TrackingContext t = fresh_copy(tc);
+      KLTTrackSequence(t, frames[s], nframes, ncols, nrows, fl[s], ft ? ft[s] : NULL, ft_col);
+      KLTFreeTrackingContext(t);
+    }
+    return;
+  }
+  if (KLT_verbose >= 1) {
+    fprintf(stderr, "(KLT) Tracking %d sequences of %d %d by %d frames, %d features in all...  ", nseq, T, ncols, nrows,
+            n);
+    fflush(stderr);
+  }
+
+  /* groups of F tracked frames: frame-major in pinned staging (the group's
+     start images first), one DMA, one device call */
+  fb = (size_t)ncols * nrows;
+  F = T < SEQ_CHUNK ? T : SEQ_CHUNK;
+  while (F > 1 && (size_t)nseq * (F + 1) * fb > MULTI_STAGE_BYTES) F--;
+  stage_bytes = (size_t)nseq * (F + 1) * fb;
+  stage = NULL;
+  if (posix_memalign((void **)&stage, 4096, stage_bytes ? stage_bytes : 1)) stage = NULL;
+  counts = (int *)malloc(sizeof(int) * nseq);
+  hx = (float *)malloc(sizeof(float) * (n + 1));
+  hy = (float *)malloc(sizeof(float) * (n + 1));
+  hv = (int *)malloc(sizeof(int) * (n + 1));
+  if (any_ft) {
+    tx = (float *)malloc(sizeof(float) * ((size_t)F * n + 1));
+    ty = (float *)malloc(sizeof(float) * ((size_t)F * n + 1));
+    tv = (int *)malloc(sizeof(int) * ((size_t)F * n + 1));
+  }
+  if (!stage || !counts || !hx || !hy || !hv || (any_ft && (!tx || !ty || !tv)))
+    KLTError("(KLTTrackSequences) Out of memory");
+  pinned = stage_bytes > 0 && klt_hip_register_host(dev, stage, stage_bytes) == 0; /* pageable still works */
+  dfr = (unsigned char *)klt_hip_malloc(dev, stage_bytes);
+  dx = (float *)klt_hip_malloc(dev, sizeof(float) * (n + 1));
+  dy = (float *)klt_hip_malloc(dev, sizeof(float) * (n + 1));
+  dv = (int *)klt_hip_malloc(dev, sizeof(int) * (n + 1));
+  if (any_ft) {
+    dtx = (float *)klt_hip_malloc(dev, sizeof(float) * ((size_t)F * n + 1));
+    dty = (float *)klt_hip_malloc(dev, sizeof(float) * ((size_t)F * n + 1));
+    dtv = (int *)klt_hip_malloc(dev, sizeof(int) * ((size_t)F * n + 1));
+  }
+  if (!dfr || !dx || !dy || !dv || (any_ft && (!dtx || !dty || !dtv))) dev_check(tc, -1, "sequences: device memory");
+  for (s = 0, k = 0; s < nseq; s++) {
+    counts[s] = fl[s]->nFeatures;
+    for (j = 0; j < counts[s]; j++, k++) {
+      hx[k] = fl[s]->feature[j]->x;
+      hy[k] = fl[s]->feature[j]->y;
+      hv[k] = fl[s]->feature[j]->val;
+    }
+  }
+  if (n > 0) {
+    dev_check(tc, klt_hip_memcpy(dev, dx, hx, sizeof(float) * n, MEMCPY_H2D), "sequences: list upload");
+    dev_check(tc, klt_hip_memcpy(dev, dy, hy, sizeof(float) * n, MEMCPY_H2D), "sequences: list upload");
+    dev_check(tc, klt_hip_memcpy(dev, dv, hv, sizeof(int) * n, MEMCPY_H2D), "sequences: list upload");
+  }
+  for (j0 = 0; j0 < T; j0 += F) {
+    const int nf = F < T - j0 ? F : T - j0;
+    for (j = 0; j <= nf; j++)
+      for (s = 0; s < nseq; s++) memcpy(stage + ((size_t)j * nseq + s) * fb, frames[s][j0 + j], fb);
+    /* synchronous: the previous group's device work is done, the staging is free again on return */
+    dev_check(tc, klt_hip_memcpy(dev, dfr, stage, (size_t)(nf + 1) * nseq * fb, MEMCPY_H2D), "sequences: upload");
+    dev_check(tc, klt_hip_track_frames_multi(dev, &D, &td, dfr, ncols, (long)(nseq * fb), (long)fb, nseq, nf, nf,
+                                             counts, dx, dy, dv, dtx, dty, dtv, n),
+              "sequences: tracking");
+    if (any_ft && n > 0) {
+      int c0 = 0;
+      dev_check(tc, klt_hip_memcpy(dev, tx, dtx, sizeof(float) * (size_t)nf * n, MEMCPY_D2H), "sequences: rows");
+      dev_check(tc, klt_hip_memcpy(dev, ty, dty, sizeof(float) * (size_t)nf * n, MEMCPY_D2H), "sequences: rows");
+      dev_check(tc, klt_hip_memcpy(dev, tv, dtv, sizeof(int) * (size_t)nf * n, MEMCPY_D2H), "sequences: rows");
+      for (s = 0; s < nseq; c0 += counts[s], s++) {
+        store_rows_ctx sr;
+        if (!ft[s]) continue;
+        sr.ft = ft[s];
+        sr.col = ft_col;
+        store_rows(&sr, j0, nf, 0, counts[s], tx + c0, ty + c0, tv + c0, n);
+      }
+    }
+  }
+  if (n > 0) {
+    dev_check(tc, klt_hip_memcpy(dev, hx, dx, sizeof(float) * n, MEMCPY_D2H), "sequences: list download");
+    dev_check(tc, klt_hip_memcpy(dev, hy, dy, sizeof(float) * n, MEMCPY_D2H), "sequences: list download");
+    dev_check(tc, klt_hip_memcpy(dev, hv, dv, sizeof(int) * n, MEMCPY_D2H), "sequences: list download");
+  } else {
+    dev_check(tc, klt_hip_sync(dev), "sequences: end");
+  }
+  for (s = 0, k = 0; s < nseq; s++)
+    for (j = 0; j < counts[s]; j++, k++) {
+      KLT_Feature ftr = fl[s]->feature[j];
+      if (ftr->val < 0) continue; /* untouched, like the reference (:1346) */
+      ftr->x = hx[k];
+      ftr->y = hy[k];
+      ftr->val = hv[k];
+      if (hv[k] != KLT_TRACKED) drop_affine(ftr);
+    }
+  if (pinned) klt_hip_unregister_host(dev, stage);
+  klt_hip_free(dev, dfr);
+  klt_hip_free(dev, dx);
+  klt_hip_free(dev, dy);
+  klt_hip_free(dev, dv);
+  klt_hip_free(dev, dtx);
+  klt_hip_free(dev, dty);
+  klt_hip_free(dev, dtv);
+  free(stage);
+  free(counts);
+  free(hx);
+  free(hy);
+  free(hv);
+  free(tx);
+  free(ty);
+  free(tv);
+
+  /* the kernel cache ends where the loop would leave it */
+  pthread_mutex_lock(&g_taps_lock);
+  g_taps = st;
+  pthread_mutex_unlock(&g_taps_lock);
+  if (KLT_verbose >= 1) {
+    int left = 0;
+    for (s = 0; s < nseq; s++) left += KLTCountRemainingFeatures(fl[s]);
+    fprintf(stderr, "\n\t%d features successfully tracked.\n", left);
+    fflush(stderr);
+  }
+}
+
+/* ------------------------------------------------------------------ */
 /* hooks for device-resident callers (bench.py, tests): the descriptors  */
 /* KLTTrackFeatures itself would use for this context                  */
 /* ------------------------------------------------------------------ */

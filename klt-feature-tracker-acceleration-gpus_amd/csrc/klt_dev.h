@@ -6,8 +6,9 @@
 //   track.hip     k_track_frames_g (the Newton loop for any window, one wave per
 //                 feature; the _g is only a name), k_band_order
 //   track7.hip    k_track7 (the Newton loop of the default configuration)
-//                 both with forward-backward instances (k_*_fb); the kernels'
-//                 bodies are track_body.h / track7_body.h
+//                 both with forward-backward instances (k_*_fb), k_track7 with
+//                 multi-sequence ones (k_track7_multi); the kernels' bodies
+//                 are track_body.h / track7_body.h
 //   affine.hip    k_affine (the affine consistency check, one frame pair per
 //                 launch); its per-feature stage is affine_dev.h, which
 //                 track.hip's k_track_frames_g_aff runs inside the batched launch
@@ -16,7 +17,8 @@
 //                 runtime.hip contexts, exit hook, uploads, setters, selection;
 //                 runtime_pyr.hip slots, banks and pyramid builds;
 //                 runtime_track.hip tracker launches, per-call and affine
-//                 entry points; runtime_frames.hip the batched calls
+//                 entry points; runtime_frames.hip the batched calls;
+//                 runtime_multi.hip the batched call over several sequences
 //
 // Kernels stay internal to their file; the runtime reaches them through the
 // launch_* functions declared here, which return the launch's hipError_t.
@@ -174,6 +176,18 @@ struct TrkFbArgs {
   long stride;  // its row stride (elements)
 };
 constexpr int kFbRejected = KLT_HIP_FB_REJECTED;
+// several independent sequences in one launch (klt_hip_track_frames_multi):
+// the multi instances take this beside TrkFramesArgs, so the others keep
+// their argument layout.  Sequence s owns features [first[s], first[s + 1]) of
+// the concatenated lists; the banks are frame-major -- frame j of sequence s
+// is pyramid j * nseq + s of a.B, the pyramid its first frame starts from is
+// pyramid s of a.A (the previous bank's last group, or the seed group) -- with
+// TrkFramesArgs::lfs the stride of one pyramid.
+constexpr int kMaxSeq = KLT_HIP_MAX_SEQUENCES;
+struct TrkMultiArgs {
+  int nseq;
+  int first[kMaxSeq + 1];
+};
 constexpr int kCountSlots = 64;  // counter pairs (the host sums them)
 constexpr int kProfN = 12;       // instrumented build: counters per wave
 
@@ -272,6 +286,9 @@ size_t track_affine_lds_bytes(int mode);
 // one wave per feature) with the latency-lean pass; band: escape checks
 hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y,
                          int *v, int n, const char **name = nullptr, const TrkFbArgs *fb = nullptr);
+// the multi-sequence instances (whole-frame interleaved pyramids, exact sums)
+hipError_t launch_track7_multi(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkMultiArgs &m, float *x,
+                               float *y, int *v, int n, const char **name = nullptr);
 // band-sorted processing order (one workgroup); count != nullptr: keep only
 // live features with own_lo <= y < own_hi and store how many
 hipError_t launch_band_order(hipStream_t st, const float *fy, const int *fv, int n, int nrows, int *perm,

@@ -400,7 +400,9 @@ int budget_chunk(klt_hip_ctx *c, const klt_hip_pyr_desc *d);
 int ensure_banks(klt_hip_ctx *c, const klt_hip_pyr_desc *d, int frames);
 int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const uint8_t *src, long pitch,
                      long stride, int F, hipStream_t st, int row_lo = 0, int row_hi = 1 << 30, int plane_lo = 0,
-                     int plane_hi = 1 << 30, int il = 1);
+                     int plane_hi = 1 << 30, int il = 1, long first = 0, long step = 1);
+// runtime_frames.hip
+bool bank_fits(const Bank &K, const klt_hip_pyr_desc *d, int F);
 // runtime_track.hip
 int check_window(klt_hip_ctx *c, const klt_hip_track_desc *d);
 void fill_trk_args(const klt_hip_track_desc *d, int nlev, int ss, int ncols, int nrows, TrkArgs &a);

@@ -306,6 +306,7 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->lazy_grad = KLT_LAZY_GRAD_DEFAULT;
   c->track_prio = 1;
   c->track_impl = 0;
+  c->track_kernel = nullptr;  // klt_hip_track_kernel: "" before the next owner's first launch
   c->fb_on = 0;
   c->fb_dist = 0.0f;
   c->fb_tab = nullptr;

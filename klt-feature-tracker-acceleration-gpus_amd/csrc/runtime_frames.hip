@@ -93,6 +93,8 @@ TrkLevel prev_level(klt_hip_ctx *c, int l) {
   return level_view(K.lv[l], c->prev.frame, K.vlo[l], K.vhi[l]);
 }
 
+}  // namespace
+
 bool bank_fits(const Bank &K, const klt_hip_pyr_desc *d, int F) {
   if (K.nlev != d->nlevels) return false;
   int w = d->ncols, h = d->nrows;
@@ -105,6 +107,8 @@ bool bank_fits(const Bank &K, const klt_hip_pyr_desc *d, int F) {
   if (d->nlevels == 2 && K.hs_cap < (size_t)(K.lv[1].w > 0 ? K.lv[1].w : 1) * d->nrows * F) return false;
   return true;
 }
+
+namespace {
 
 // one level (a view: a slot's, or a bank frame's) into frame f of level `to`
 // (a slot's: f = 0), in its layout

@@ -305,9 +305,12 @@ int ensure_banks(klt_hip_ctx *c, const klt_hip_pyr_desc *d, int frames) {
 // row_lo/row_hi: the level-0 rows to build (the sigma-3.6 rows pass hs over
 // all of them); plane_lo/plane_hi: the rows whose level-0 planes are stored
 // (a band's outer margin feeds only level 1)
+// first / step: frame f goes to pyramid first + f * step of the bank (the
+// frame-major banks of klt_hip_track_frames_multi: one sequence's frames are
+// nseq pyramids apart); the caller keeps first + (F - 1) * step < K.frames
 int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const uint8_t *src, long pitch,
                      long stride, int F, hipStream_t st, int row_lo, int row_hi, int plane_lo, int plane_hi,
-                     int il) {
+                     int il, long first, long step) {
   const int W = d->ncols, H = d->nrows;
   const DefTaps T = default_taps(d);
   const bool two = d->nlevels == 2;
@@ -328,8 +331,10 @@ int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const u
   for (int l = 0; l < d->nlevels; ++l) K.lv[l].il = l == 0 ? il : il1;
   {
     TimedScope ts(c, T_L0, st, F);
-    if (launch_l0(c, st, src, pitch, stride, W, H, T, vec_u8, vec_out, K.lv[0].img, K.lv[0].gx, K.lv[0].gy, K.hs, W1,
-                  (two && W1 > 0) ? 1 : 0, np0 * fs0, fsh, F, r0, r1, &p0, &p1, il))
+    const long o0 = first * np0 * fs0;
+    if (launch_l0(c, st, src, pitch, stride, W, H, T, vec_u8, vec_out, K.lv[0].img + o0, K.lv[0].gx + o0,
+                  K.lv[0].gy + o0, K.hs + first * fsh, W1, (two && W1 > 0) ? 1 : 0, step * np0 * fs0, step * fsh, F, r0,
+                  r1, &p0, &p1, il))
       return -1;
   }
   K.vlo[0] = p0;
@@ -351,8 +356,10 @@ int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const u
       HMARK_IN("l0_launched");
       TimedScope ts(c, T_L1, st, F);
       const int vec = (W1 % 4 == 0 && W1 >= 8) ? 1 : 0;
-      if (launched(c, "k_pyr_l1", launch_pyr_l1(st, K.hs, W1, H, H1, T, vec, K.lv[1].img, K.lv[1].gx, K.lv[1].gy, fsh,
-                                                np * fs1, F, t1lo, t1hi, il1)))
+      const long o1 = first * np * fs1;
+      if (launched(c, "k_pyr_l1", launch_pyr_l1(st, K.hs + first * fsh, W1, H, H1, T, vec, K.lv[1].img + o1,
+                                                K.lv[1].gx + o1, K.lv[1].gy + o1, step * fsh, step * np * fs1, F, t1lo,
+                                                t1hi, il1)))
         return -1;
       HMARK_IN("l1_launched");
     }

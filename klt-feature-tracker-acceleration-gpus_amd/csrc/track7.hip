@@ -399,6 +399,30 @@ __device__ __forceinline__ Lev lev_prev(const TrkArgs &a, const TrkFramesArgs &b
              f ? P.h : Q.h, f ? P.vlo : Q.vlo, f ? P.vhi : Q.vhi, a.oobx[r], a.ooby[r], f ? P.il : Q.il};
 }
 
+// The two images of frame j at level r.  MULTI (k_track7_multi): the launch
+// carries nsq sequences through frame-major banks, the wave's feature belongs
+// to sequence sq (wave-uniform, scalar): image 2 is pyramid j * nsq + sq of
+// a.B, image 1 pyramid (j - 1) * nsq + sq of it or, for the launch's first
+// frame, pyramid sq of a.A (a group laid out like a bank's: same level sizes,
+// layout and pyramid stride).  Offsets in 64 bits.  Otherwise lev_of / lev_prev
+// as they stand.
+template <bool MULTI>
+__device__ __forceinline__ Lev lev_cur(const TrkArgs &a, const TrkFramesArgs &b, int r, int j, int sq, int nsq) {
+  if constexpr (MULTI) return lev_of(a.B[r], ((long)j * nsq + sq) * b.lfs[r], a.oobx[r], a.ooby[r]);
+  else return lev_of(a.B[r], (long)j * b.lfs[r], a.oobx[r], a.ooby[r]);
+}
+template <bool MULTI>
+__device__ __forceinline__ Lev lev_before(const TrkArgs &a, const TrkFramesArgs &b, int r, int j, int sq, int nsq) {
+  if constexpr (MULTI) {
+    const TrkLevel &P = a.A[r], &Q = a.B[r];
+    const bool f = j == 0;
+    const long off = (f ? (long)sq : (long)(j - 1) * nsq + sq) * b.lfs[r];
+    return Lev{(f ? P.img : Q.img) + off, nullptr, nullptr, Q.w, Q.h, Q.vlo, Q.vhi, a.oobx[r], a.ooby[r], Q.il};
+  } else {
+    return lev_prev(a, b, r, j);
+  }
+}
+
 // band-built pyramids (klt_hip_track_frames_band): every row the window's
 // bilinear samples touch must have been built
 __device__ __forceinline__ bool band_bad(const Lev &L, float y) {
@@ -723,8 +747,9 @@ __global__ __launch_bounds__(kBlock, LAZY && NL == 2 ? 5 : LAZY ? 4 : 1) void k_
                                                    float *__restrict__ fy, int *__restrict__ fv, int n) {
   static_assert(!LAZY || (AOS && !BAND), "lazy gradients: whole-frame interleaved pyramids");
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF + (LAZY ? kPat : 0)];
-  constexpr bool FB = false, HOOK = false;
+  constexpr bool FB = false, HOOK = false, MULTI = false;
   const TrkFbArgs fb{};
+  const TrkMultiArgs ms{};
 #include "track7_body.h"
 }
 
@@ -737,8 +762,9 @@ __global__ __launch_bounds__(kBlock, NL == 2 ? 5 : 4) void k_track7_hook(TrkArgs
                                                                           float *__restrict__ fy,
                                                                           int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF + kPat];
-  constexpr bool BAND = false, AOS = true, LAZY = true, FB = false, HOOK = true;
+  constexpr bool BAND = false, AOS = true, LAZY = true, FB = false, HOOK = true, MULTI = false;
   const TrkFbArgs fb{};
+  const TrkMultiArgs ms{};
 #include "track7_body.h"
 }
 
@@ -748,7 +774,24 @@ __global__ __launch_bounds__(kBlock) void k_track7_fb(TrkArgs a, TrkFramesArgs b
                                                       float *__restrict__ fx, float *__restrict__ fy,
                                                       int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
-  constexpr bool BAND = false, FAST = false, FB = true, LAZY = false, HOOK = false;
+  constexpr bool BAND = false, FAST = false, FB = true, LAZY = false, HOOK = false, MULTI = false;
+  const TrkMultiArgs ms{};
+#include "track7_body.h"
+}
+
+// the multi-sequence instances (klt_hip_track_frames_multi): whole-frame
+// interleaved pyramids with full level-0 records, exact sums.  Kernels of their
+// own with the sequences' first features beside TrkFramesArgs, so that every
+// other instance keeps its arguments and stays the code it was; in the body
+// only the wave's sequence lookup and the level bases differ (lev_cur /
+// lev_before).
+template <int NL>
+__global__ __launch_bounds__(kBlock) void k_track7_multi(TrkArgs a, TrkFramesArgs b, TrkMultiArgs ms,
+                                                         float *__restrict__ fx, float *__restrict__ fy,
+                                                         int *__restrict__ fv, int n) {
+  __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
+  constexpr bool BAND = false, AOS = true, FAST = false, FB = false, LAZY = false, HOOK = false, MULTI = true;
+  const TrkFbArgs fb{};
 #include "track7_body.h"
 }
 
@@ -777,6 +820,26 @@ static int oob_threshold(int n) {
     else lo = mid;
   }
   return hi;
+}
+
+hipError_t launch_track7_multi(hipStream_t st, const TrkArgs &a_in, const TrkFramesArgs &b, const TrkMultiArgs &m,
+                               float *x, float *y, int *v, int n, const char **name) {
+  // the runtime sends interleaved full-record levels of one size in A and B,
+  // exact sums, and first[] ascending from 0 to n
+  if (!a_in.aos || a_in.fast || a_in.lazy || a_in.escape || m.nseq < 1 || m.nseq > kMaxSeq || m.first[0] != 0 ||
+      m.first[m.nseq] != n || b.perm || b.n_dev || b.xcd_per)
+    return hipErrorInvalidValue;
+  TrkArgs a = a_in;
+  for (int l = 0; l < KLT_HIP_MAX_LEVELS; ++l) {
+    a.oobx[l] = oob_threshold(a.B[l].w);
+    a.ooby[l] = oob_threshold(a.B[l].h);
+  }
+  const int grid = (n + kWaves - 1) / kWaves;
+  const bool two = KLT_T7_NL2 && a.nlev == 2;
+  if (name) *name = two ? "kltdev::k_track7_multi<2>" : "kltdev::k_track7_multi<0>";
+  if (two) hipLaunchKernelGGL((k_track7_multi<2>), dim3(grid), dim3(kBlock), 0, st, a, b, m, x, y, v, n);
+  else hipLaunchKernelGGL((k_track7_multi<0>), dim3(grid), dim3(kBlock), 0, st, a, b, m, x, y, v, n);
+  return hipGetLastError();
 }
 
 hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const TrkFramesArgs &b, float *x, float *y,

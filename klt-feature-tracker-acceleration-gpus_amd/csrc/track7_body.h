@@ -2,8 +2,9 @@
 // included inside each kernel: the FB-off kernels keep their by-value
 // arguments and compile to what they were before the forward-backward
 // instances existed.  The including kernel provides: the template parameters
-// BAND, AOS, NL, FAST, LAZY, HOOK; constexpr bool FB; TrkArgs a; TrkFramesArgs b;
-// TrkFbArgs fb; fx, fy, fv, n; and the LDS array red_all.
+// BAND, AOS, NL, FAST, LAZY, HOOK; constexpr bool FB, MULTI; TrkArgs a;
+// TrkFramesArgs b; TrkFbArgs fb; TrkMultiArgs ms; fx, fy, fv, n; and the LDS
+// array red_all.
   if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   if constexpr (HOOK)
@@ -22,6 +23,21 @@
     return;
   }
   const int f = u(b.perm ? b.perm[slot] : slot);
+  // MULTI: the sequence of this wave's feature -- a wave's own lookup (the
+  // four features of a workgroup may belong to different sequences), by
+  // bisection over the sequences' first features, scalar throughout:
+  // first[sq] <= f < first[sq + 1], empty sequences skipped
+  int sq = 0, nsq = 1;
+  if constexpr (MULTI) {
+    nsq = ms.nseq;
+    int hi = nsq;
+    while (hi - sq > 1) {
+      const int mid = (sq + hi) >> 1;
+      if (f >= ms.first[mid]) sq = mid;
+      else hi = mid;
+    }
+    sq = u(sq);
+  }
   float *red = red_all[wave];
   for (int i = lane; i < kRedF; i += kWave) red[i] = 0.0f;  // pads stay +0
   wave_lds_sync();
@@ -48,7 +64,7 @@
     int rstat = kTracked;
     if (v >= 0 || job) {
       // one frame of KLTTrackFeatures for this feature (:1348-1437)
-      const Lev R = lev_prev(a, b, 0, j);
+      const Lev R = lev_before<MULTI>(a, b, 0, j, sq, nsq);
       // the corners kept from frame j-1 serve this frame's level 0 only: a frame
       // that does not reach level 0 leaves nothing for the one after it
       const unsigned cpx = carry.px;
@@ -68,8 +84,8 @@
         yl = u(yl * a.ss);
         xo = u(xo * a.ss);
         yo = u(yo * a.ss);
-        const Lev LA = lev_prev(a, b, r, j);
-        const Lev LB = lev_of(a.B[r], (long)j * b.lfs[r], a.oobx[r], a.ooby[r]);
+        const Lev LA = lev_before<MULTI>(a, b, r, j, sq, nsq);
+        const Lev LB = lev_cur<MULTI>(a, b, r, j, sq, nsq);
         const bool lj = job && r == nlev - 1;
         T7_T(t_l0);
         if (LAZY && r == 0)

@@ -13,6 +13,7 @@ MAX_TAPS = 71
 MAX_LEVELS = 8
 EXACT, FAST = 0, 1
 FB_REJECTED = -6  # KLT_HIP_FB_REJECTED: lost to the forward-backward check (klt_hip_set_fb)
+MAX_SEQUENCES = 64  # KLT_HIP_MAX_SEQUENCES: klt_hip_track_frames_multi's nseq
 
 
 class Taps(C.Structure):
@@ -128,6 +129,10 @@ DEVICE_PROTOS = {
     "klt_hip_frames_end_slot": (C.c_int, [V, C.c_int]),
     "klt_hip_track_frames": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc), V, C.c_long, C.c_long,
                                        C.c_int, C.c_int, V, V, V, C.c_int, V, V, V, C.c_long]),
+    # n_seq: host int[nseq]
+    "klt_hip_track_frames_multi": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc), V, C.c_long, C.c_long,
+                                             C.c_long, C.c_int, C.c_int, C.c_int, IP, V, V, V, V, V, V, C.c_long]),
+    "klt_hip_multi_covers": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc)]),
     # frames: const unsigned char *const *; rows: klt_hip_rows_fn or NULL
     "klt_hip_track_frames_host": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc), V, C.c_int, C.c_int,
                                             C.c_int, V, V, V, C.c_int, V, V]),
