@@ -130,7 +130,8 @@ int klt_hip_build_pyramid(klt_hip_ctx *ctx, int slot, const klt_hip_pyr_desc *de
    fused kernels apply (they must agree bit for bit) */
 int klt_hip_set_path(klt_hip_ctx *ctx, int force_generic);
 /* tuning hook: 1 tracks features in input order; 0 (default) in row-band
-   order with each XCD given one band (L2 locality).  Results do not depend on it.
+   order with each XCD given one band (L2 locality) and its share of the lost
+   features (klt_hip_order_slot).  Results do not depend on it.
    Either call also drops the cached band order (reused by short calls while it
    covers at most 32 tracked frames), so the next call sorts afresh. */
 int klt_hip_set_track_order(klt_hip_ctx *ctx, int input_order);
@@ -264,7 +265,7 @@ size_t klt_hip_ctx_footprint(klt_hip_ctx *ctx);
    value for every context of the process (A/B in one tree). */
 int klt_hip_set_frames_overlap(klt_hip_ctx *ctx, int overlap);
 /* schedule 3: the tracker waves that may still be running when the next
-   chunk's build is released (default 3072, three per SIMD; 0: none, the build
+   chunk's build is released (default 4096, four per SIMD; 0: none, the build
    follows the tracker).  A launch of no more waves than this is not waited
    for.  KLT_FRAMES_TAIL=K in the environment replaces it. */
 int klt_hip_set_frames_tail(klt_hip_ctx *ctx, int waves_left);
@@ -275,11 +276,33 @@ int klt_hip_set_frames_tail(klt_hip_ctx *ctx, int waves_left);
 int klt_hip_tail_threshold(unsigned base, unsigned launched, unsigned waves_left, unsigned *threshold);
 /* measurement hook, off (NULL) by default: a device buffer of 4 + 2 * cap
    u64, zeroed but for [2] = cap, that every k_track7 launch fills with its
-   waves' wall_clock64() (100 MHz) times: [0] / [1] count the waves that have
-   entered / left, [4 + k] is the k-th entry time and [4 + cap + k] the k-th
-   exit time, each list in time order and not paired (the sum of the wave
-   durations is the difference of the two sums). */
+   waves' wall_clock64() (100 MHz) times: [4 + k] is the entry time of wave k
+   of the launch's grid (4 * workgroup + wave in the workgroup), [4 + cap + i]
+   the exit time of the wave that tracked feature i, or that had slot i >= n
+   of the processing order and no feature.  The two lists are not paired (the
+   sum of the wave durations is the difference of the two sums); an index >=
+   cap leaves no time, a place no wave wrote stays 0, and [0], [1] and [3] are
+   not written.  Bits 60..63 of every time hold the XCD the wave ran on (the
+   hardware's XCC_ID), bits 0..59 the time.  The waves share no counter, so
+   that the hook does not hold them back. */
 int klt_hip_set_wave_times(klt_hip_ctx *ctx, void *dev);
+/* The processing order's balanced layout, host only (the arithmetic
+   k_band_order uses on the device).  A tracker launch over n features hands
+   XCD x the slots [min(x S, n), min((x + 1) S, n)) with S = 4 * xcd_per.  With
+   n_live live features in band order and n - n_live lost ones, segment x
+   starts with the live ranks [B_x, B_{x+1}), B_x = floor(n_live * min(x S, n)
+   / n), and is filled up with lost ranks in order.  Writes the slot of live
+   rank `rank` (lost = 0, rank < n_live) or of lost rank `rank` (lost = 1,
+   rank < n - n_live) to *slot and returns 0; -1 for arguments outside that
+   (n < 1, 8 S < n, n_live outside 0..n, a rank out of range, slot NULL). */
+int klt_hip_order_slot(int n, int xcd_per, int n_live, int rank, int lost, int *slot);
+/* test hook: runs the processing-order kernel (k_band_order) as a whole-frame
+   tracker launch over n features would -- y and val are device arrays, nrows
+   the image height -- and copies the order (slot -> feature) to the host
+   array perm_out[n].  Synchronous.  KLT_ORDER_BALANCE=0 in the environment
+   (read once, A/B only) restores the earlier layout, live features in band
+   order and all lost ones last, for every order of the process. */
+int klt_hip_band_order_probe(klt_hip_ctx *ctx, const float *y, const int *val, int n, int nrows, int *perm_out);
 /* 1 if pyramids for `desc` would be built by the fused gfx950 kernels, else 0 */
 int klt_hip_fused_path(klt_hip_ctx *ctx, const klt_hip_pyr_desc *desc);
 /* 1 if the slot was built by the fused gfx950 kernels, 0 generic, <0 invalid */

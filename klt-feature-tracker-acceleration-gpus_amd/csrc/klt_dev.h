@@ -161,9 +161,9 @@ struct TrkFramesArgs {
   // waves of this launch are gone" (klt_hip_set_frames_overlap's tail
   // schedule).  The count itself is in device memory: 5024 system-scope adds
   // to signal memory took 4.6 ms per launch.
-  // wave_t: {entered, left, capacity, 0}, then `capacity` entry times and
-  // `capacity` exit times (wall_clock64), each list in arrival order
-  // (klt_hip_set_wave_times)
+  // wave_t: {0, 0, capacity, 0}, then `capacity` entry times and
+  // `capacity` exit times (wall_clock64, the XCD in the top four bits), by
+  // the wave's number in the grid and by its feature (klt_hip_set_wave_times)
   unsigned *exits, *exit_sig;
   unsigned exit_thr;
   unsigned long long *wave_t;
@@ -289,10 +289,50 @@ hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a, const TrkF
 // the multi-sequence instances (whole-frame interleaved pyramids, exact sums)
 hipError_t launch_track7_multi(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkMultiArgs &m, float *x,
                                float *y, int *v, int n, const char **name = nullptr);
+// The balanced layout of the processing order (k_band_order, klt_hip_order_slot).
+// The trackers take blocks XCD-major, so XCD x processes the slots of segment
+// x, [min(x S, n), min((x + 1) S, n)) with S = seg.  Live features keep their
+// band order and fill the head of each segment in shares proportional to its
+// capacity, lost features fill the rest: the waves that leave at once are
+// spread over all eight XCDs instead of emptying the last ones.
+constexpr int kXcds = 8;
+// live[x]: live rank at which segment x starts, B_x = floor(n_live * min(x S, n) / n)
+// lost[x]: lost rank at which it starts, the prefix sum of capacity - live share
+__host__ __device__ __forceinline__ int order_seg_start(int n, int seg, int x) {
+  const long e = (long)x * seg;
+  return e < n ? (int)e : n;
+}
+__host__ __device__ __forceinline__ int order_live_start(int n, int seg, int n_live, int x) {
+  return n > 0 ? (int)((unsigned long long)n_live * (unsigned)order_seg_start(n, seg, x) / (unsigned)n) : 0;
+}
+__host__ __device__ __forceinline__ int order_lost_start(int n, int seg, int n_live, int x) {
+  return order_seg_start(n, seg, x) - order_live_start(n, seg, n_live, x);
+}
+// the slot of live rank `rank` (lost = false) or lost rank `rank` (true),
+// given the eight segment starts of its kind and the live starts
+__host__ __device__ __forceinline__ int order_slot_of(const int *live, const int *lost_st, int seg, int rank,
+                                                      bool lost) {
+  const int *st = lost ? lost_st : live;
+  // the last segment that starts at or before the rank (the starts never
+  // decrease, and an empty segment starts where the next one does); constant
+  // indices only, so that the starts can live in registers
+  int x = 0, start = st[0], head = live[1] - live[0];
+#pragma unroll
+  for (int k = 1; k < kXcds; ++k) {
+    const bool in = rank >= st[k];
+    x = in ? k : x;
+    start = in ? st[k] : start;
+    head = in ? live[k + 1] - live[k] : head;
+  }
+  return x * seg + (lost ? head : 0) + (rank - start);  // a segment's lost features follow its live ones
+}
+
 // band-sorted processing order (one workgroup); count != nullptr: keep only
-// live features with own_lo <= y < own_hi and store how many
+// live features with own_lo <= y < own_hi and store how many.  seg > 0 (and
+// count == nullptr): the balanced layout over segments of seg slots; 0: live
+// features in band order, lost features last
 hipError_t launch_band_order(hipStream_t st, const float *fy, const int *fv, int n, int nrows, int *perm,
-                             float own_lo, float own_hi, int *count);
+                             float own_lo, float own_hi, int *count, int seg);
 
 hipError_t launch_affine(hipStream_t st, const AffArgs &a);
 

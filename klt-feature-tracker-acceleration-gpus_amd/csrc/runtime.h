@@ -85,13 +85,17 @@ struct PrevRef {
 
 // klt_hip_set_frames_overlap's values
 enum { kSchedOne = 0, kSchedAuto = 1, kSchedBeside = 2, kSchedTail = 3 };
-// klt_hip_set_frames_tail's default: three of a SIMD's five lazy-gradient
-// tracker waves (256 CUs x 4 SIMDs), which leaves registers for three pyramid
-// waves beside them.  1080p / 5000, headline frames/s over one stream: K = 512
+// klt_hip_set_frames_tail's default: four of a SIMD's five lazy-gradient
+// tracker waves (256 CUs x 4 SIMDs).  1080p / 5000, headline frames/s over
+// one stream with the lost features last in the processing order: K = 512
 // 1.00, 1024 1.03, 2048 1.05, 3072 and 3584 1.06; 4096 and 4608 1.07 in the
 // median but with single runs back at one stream's speed
-// (profiles/sched_tail_bound.txt)
-constexpr int kTailLeftDefault = 3072;
+// (profiles/sched_tail_bound.txt).  With the balanced order every SIMD frees
+// registers as features die, and over K = 3072: 2048 1.00, 3584 1.01-1.02,
+// 4096 1.02-1.03 with its slowest run above 3072's fastest in both sweeps,
+// 4608 1.02 with one low run, no wait at all 0.87
+// (profiles/order_balance_headline_ab.txt)
+constexpr int kTailLeftDefault = 4096;
 // the exit counter is re-based (at a drained point) once it has passed this;
 // past it, and for launches of this many features, no launch counts, so the
 // count stays below 2^31 whatever the call's length

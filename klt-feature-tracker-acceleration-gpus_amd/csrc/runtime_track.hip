@@ -41,7 +41,54 @@ constexpr int kOrderMin = 2048;
 // results) is re-sorted once it covers this many tracked frames; features
 // move about a pixel per frame, the XCDs' row bands are ~H/8 rows tall
 constexpr int kOrderMaxAge = 32;
+
+// KLT_ORDER_BALANCE=0 in the environment (A/B in one tree, read once): the
+// order keeps the lost features last instead of spreading them over the XCDs
+bool order_balanced() {
+  static const bool on = [] {
+    const char *v = getenv("KLT_ORDER_BALANCE");
+    return !(v && *v && atoi(v) == 0);
+  }();
+  return on;
+}
+
+// slots per XCD of a tracker launch over n features in XCD-major order
+// (TrkFramesArgs::xcd_per workgroups of kBlock / kWave waves)
+int order_xcd_per(int n) {
+  const int per = kBlock / kWave, nb = (n + per - 1) / per;
+  return (nb + 7) / 8;
+}
 }  // namespace
+
+KLT_API int klt_hip_order_slot(int n, int xcd_per, int n_live, int rank, int lost, int *slot) {
+  if (n < 1 || xcd_per < 1 || n_live < 0 || n_live > n || rank < 0 || !slot) return -1;
+  const long seg = (long)xcd_per * (kBlock / kWave);
+  if (seg * kXcds < n || seg > INT32_MAX / kXcds) return -1;  // the eight segments hold every slot
+  if (rank >= (lost ? n - n_live : n_live)) return -1;
+  int live_st[kXcds + 1], lost_st[kXcds + 1];
+  for (int x = 0; x <= kXcds; ++x) {
+    live_st[x] = order_live_start(n, (int)seg, n_live, x);
+    lost_st[x] = order_lost_start(n, (int)seg, n_live, x);
+  }
+  *slot = order_slot_of(live_st, lost_st, (int)seg, rank, lost != 0);
+  return 0;
+}
+
+KLT_API int klt_hip_band_order_probe(klt_hip_ctx *c, const float *y, const int *v, int n, int nrows, int *perm_out) {
+  if (!c) return fail(c, "band_order_probe: null context");
+  if (n < 1 || !y || !v || !perm_out) return fail(c, "band_order_probe: n %d, or a null array", n);
+  if (use_device(c)) return -1;
+  int *d = nullptr;
+  HIPCHK(c, hipMalloc((void **)&d, sizeof(int) * (size_t)n));
+  const int seg = order_balanced() ? order_xcd_per(n) * (kBlock / kWave) : 0;
+  hipError_t e = hipMemsetAsync(d, 0xFF, sizeof(int) * (size_t)n, c->stream);  // a slot left unwritten reads -1
+  if (e == hipSuccess) e = launch_band_order(c->stream, y, v, n, nrows, d, 0.0f, 0.0f, nullptr, seg);
+  if (e == hipSuccess) e = hipMemcpyAsync(perm_out, d, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(c, "band_order_probe: %s", hipGetErrorString(e));
+  return 0;
+}
 
 // the default configuration's latency-lean tracker (track7.hip) serves this
 // launch: 7x7 window, exact sums, no gain/bias, the lane-patch path on, and
@@ -80,8 +127,9 @@ int order_features(klt_hip_ctx *c, hipStream_t st, int nrows, const float *y, co
       timespec t0_, t1_;
       clock_gettime(CLOCK_MONOTONIC, &t0_);
 #endif
+      const int seg = !own && order_balanced() ? order_xcd_per(n) * (kBlock / kWave) : 0;
       if (launched(c, "k_band_order", launch_band_order(st, y, v, n, nrows, c->d_perm, own ? own[0] : 0.0f,
-                                                        own ? own[1] : 0.0f, own ? c->d_count : (int *)nullptr)))
+                                                        own ? own[1] : 0.0f, own ? c->d_count : (int *)nullptr, seg)))
         return -1;
 #ifdef KLT_HOST_PROF
       clock_gettime(CLOCK_MONOTONIC, &t1_);
@@ -92,9 +140,8 @@ int order_features(klt_hip_ctx *c, hipStream_t st, int nrows, const float *y, co
       c->perm_age = nframes;
     }
     if (own) bb.n_dev = c->d_count;
-    const int per = kBlock / kWave, nb = (n + per - 1) / per;
     bb.perm = c->d_perm;
-    bb.xcd_per = (nb + 7) / 8;
+    bb.xcd_per = order_xcd_per(n);
   }
   return 0;
 }

@@ -780,8 +780,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PPL == 1
 
 // ---------------------------------------------------------------------------
 // k_band_order: processing order for the tracker -- live features bucketed by
-// image row band (counting sort, one workgroup), lost features last.  Only
-// the order of work changes; every feature's result is independent of it.
+// image row band (counting sort, one workgroup).  seg == 0: lost features
+// last.  seg > 0: the balanced layout (klt_dev.h, order_slot_of) -- the
+// trackers hand segment x of seg slots to XCD x, so each segment gets its
+// share of the live features, still in band order, and is filled up with lost
+// ones; the eight segment starts are worked out once after the scan and only
+// the scatter positions differ.  Only the order of work changes; every
+// feature's result is independent of it.
 // It sits between two tracker launches on the tracking stream, so it is
 // shaped for latency: kPer features per thread loaded before any is used, the
 // buckets kept in LDS for the second pass, features outside a rank's band
@@ -804,12 +809,14 @@ __device__ __forceinline__ int wave_claim(int *ctr, unsigned long long mine) {
 __global__ __launch_bounds__(kSortThreads) void k_band_order(const float *__restrict__ fy,
                                                              const int *__restrict__ fv, int n, int nrows,
                                                              int *__restrict__ perm, float own_lo, float own_hi,
-                                                             int *__restrict__ count) {
+                                                             int *__restrict__ count, int seg) {
   __builtin_amdgcn_s_setprio(3);  // on the chain between two tracker launches
   // count != nullptr: keep only live features with own_lo <= y < own_hi (a
   // rank's band in sharded mode), *count = how many; else every feature
   __shared__ int cnt[kBands + 2];
+  __shared__ int seg_live[kXcds + 1], seg_lost[kXcds + 1];
   __shared__ unsigned char bk[kBucketCache];
+  const bool bal = seg > 0 && !count;  // a band's order is compacted to the kept features and balanced by n_dev
   const int t = threadIdx.x;
   for (int i = t; i <= kBands + 1; i += kSortThreads) cnt[i] = 0;
   __syncthreads();
@@ -857,16 +864,37 @@ __global__ __launch_bounds__(kSortThreads) void k_band_order(const float *__rest
       const int o = __shfl_up(inc, d, kWave);
       if (t >= d) inc += o;
     }
-    int run = inc - sum;
+    int run = inc - sum, n_live = 0;
 #pragma unroll
     for (int k = 0; k < kPerLane; ++k) {
       const int j = t * kPerLane + k;
       if (j <= kBands + 1) cnt[j] = run;
+      if (j == kBands) n_live = run;  // start of the lost bucket
       run += c[k];
+    }
+    if (bal) {
+      n_live = __shfl(n_live, kBands / kPerLane, kWave);
+      if (t <= kXcds) {
+        seg_live[t] = order_live_start(n, seg, n_live, t);
+        seg_lost[t] = order_lost_start(n, seg, n_live, t);
+      }
     }
   }
   __syncthreads();
   if (count && t == 0) *count = cnt[kBands + 1];  // start of the excluded bucket = kept features
+  int sl[kXcds + 1], so[kXcds + 1];
+  if (bal) {
+#pragma unroll
+    for (int k = 0; k <= kXcds; ++k) {
+      sl[k] = seg_live[k];
+      so[k] = seg_lost[k];
+    }
+  }
+  // rank within the live or the lost features -> slot (every slot < n: order_slot_of)
+  auto place = [&](int rank, bool lost, int i) {
+    const int s = !bal ? rank : order_slot_of(sl, so, seg, lost ? rank - sl[kXcds] : rank, lost);
+    if ((unsigned)s < (unsigned)n) perm[s] = i;
+  };
   // pass 2: scatter
   for (int i0 = 0; i0 < n; i0 += kStep) {
     int b[kPer];
@@ -879,8 +907,8 @@ __global__ __launch_bounds__(kSortThreads) void k_band_order(const float *__rest
     for (int k = 0; k < kPer; ++k) {
       const int i = i0 + k * kSortThreads + t;
       const unsigned long long lost = __ballot(b[k] == kBands);
-      if (b[k] == kBands) perm[wave_claim(&cnt[kBands], lost)] = i;
-      else if (b[k] < kBands) perm[atomicAdd(&cnt[b[k]], 1)] = i;
+      if (b[k] == kBands) place(wave_claim(&cnt[kBands], lost), true, i);
+      else if (b[k] < kBands) place(atomicAdd(&cnt[b[k]], 1), false, i);
     }
   }
 }
@@ -976,8 +1004,9 @@ hipError_t launch_track_frames(hipStream_t st, bool exact, bool li, bool patch, 
 }
 
 hipError_t launch_band_order(hipStream_t st, const float *fy, const int *fv, int n, int nrows, int *perm,
-                             float own_lo, float own_hi, int *count) {
-  hipLaunchKernelGGL(k_band_order, dim3(1), dim3(kSortThreads), 0, st, fy, fv, n, nrows, perm, own_lo, own_hi, count);
+                             float own_lo, float own_hi, int *count, int seg) {
+  hipLaunchKernelGGL(k_band_order, dim3(1), dim3(kSortThreads), 0, st, fy, fv, n, nrows, perm, own_lo, own_hi, count,
+                     seg);
   return hipGetLastError();
 }
 

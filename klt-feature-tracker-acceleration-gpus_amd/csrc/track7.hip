@@ -449,15 +449,27 @@ struct Counts {
 // times and the optional count of the waves that have left (TrkFramesArgs::
 // wave_t / ::exits).  The count is a scheduling hint: nothing in the kernel
 // waits for it, and the one store to signal memory (read by the command
-// processor, hipStreamWaitValue32) is relaxed at system scope.  The sum of the
-// wave durations and both time distributions need no pairing of the lists.
-__device__ __forceinline__ void wave_time(unsigned long long *wave_t, int which) {
-  const unsigned long long t = wall_clock64(), k = atomicAdd(&wave_t[which], 1ull), cap = wave_t[2];
-  if (k < cap) wave_t[4 + which * cap + k] = t;
+// processor, hipStreamWaitValue32) is relaxed at system scope.  The times
+// take no place in a list by counting: 5024 adds to one word, serialised
+// between the XCDs, held every wave of a launch back -- by up to 220 us when
+// each wave waited for its place, lost features included, and still by 55 us
+// without a result.  A wave's entry time goes to its number in the grid, its
+// exit time to a number it has at hand when it leaves, so that the kernel
+// body keeps nothing alive for the hook: its feature's index, or its slot
+// when that holds no feature (slots past n: no feature has that index).  A
+// band launch's waves past their XCD's run leave under their number in the
+// grid, which a feature may share.
+constexpr int kWaveXcdShift = 60;
+constexpr unsigned long long kWaveTimeMask = (1ull << kWaveXcdShift) - 1ull;
+__device__ __forceinline__ void wave_time(unsigned long long *wave_t, int which, unsigned k) {
+  const unsigned long long t = wall_clock64(), cap = wave_t[2];
+  // the wave's XCD (XCC_ID, as pyramid.hip's PYR_END reads it) rides in the top four bits of its times
+  const unsigned long long xcd = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u;
+  if (k < cap) wave_t[4 + which * cap + k] = (t & kWaveTimeMask) | (xcd << kWaveXcdShift);
 }
-__device__ __forceinline__ void wave_exit(const TrkFramesArgs &b, int lane) {
+__device__ __forceinline__ void wave_exit(const TrkFramesArgs &b, int lane, unsigned k) {
   if (lane != 0) return;
-  if (b.wave_t) wave_time(b.wave_t, 1);
+  if (b.wave_t) wave_time(b.wave_t, 1, k);
   if (b.exits) {
     const unsigned k = atomicAdd(b.exits, 1u) + 1u;
     if (k == b.exit_thr) __hip_atomic_store(b.exit_sig, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -8,18 +8,18 @@
   if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   if constexpr (HOOK)
-    if (b.wave_t && lane == 0) wave_time(b.wave_t, 0);
+    if (b.wave_t && lane == 0) wave_time(b.wave_t, 0, blockIdx.x * kWaves + wave);
   if (b.n_dev) n = *b.n_dev;
   // XCD-major block order over the (band-sorted) features actually processed
   const int xcd_per = b.n_dev && b.xcd_per > 0 ? ((n + kWaves - 1) / kWaves + 7) / 8 : b.xcd_per;
   if (xcd_per > 0 && (int)(blockIdx.x / 8) >= xcd_per) {
-    if constexpr (HOOK) wave_exit(b, lane);
+    if constexpr (HOOK) wave_exit(b, lane, blockIdx.x * kWaves + wave);
     return;
   }
   const int blk = xcd_per > 0 ? (int)(blockIdx.x % 8) * xcd_per + (int)(blockIdx.x / 8) : (int)blockIdx.x;
   const int slot = blk * kWaves + wave;
   if (slot >= n) {  // whole wave; no workgroup barrier in this kernel
-    if constexpr (HOOK) wave_exit(b, lane);
+    if constexpr (HOOK) wave_exit(b, lane, slot);
     return;
   }
   const int f = u(b.perm ? b.perm[slot] : slot);
@@ -199,4 +199,4 @@
       atomicAdd(&b.count[kCountSlots + k], (unsigned long long)cnt.passes);
     }
   }
-  if constexpr (HOOK) wave_exit(b, lane);
+  if constexpr (HOOK) wave_exit(b, lane, f);

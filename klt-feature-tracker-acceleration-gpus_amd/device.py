@@ -109,6 +109,8 @@ DEVICE_PROTOS = {
     "klt_hip_set_frames_tail": (C.c_int, [V, C.c_int]),
     "klt_hip_tail_threshold": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint)]),
     "klt_hip_set_wave_times": (C.c_int, [V, V]),
+    "klt_hip_order_slot": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, IP]),
+    "klt_hip_band_order_probe": (C.c_int, [V, V, V, C.c_int, C.c_int, V]),
     "klt_hip_set_host_threads": (C.c_int, [V, C.c_int]),
     "klt_hip_get_host_threads": (C.c_int, [V]),
     "klt_hip_set_path": (C.c_int, [V, C.c_int]),
