@@ -61,6 +61,28 @@ int klt_amd_set_fb_check(KLT_TrackingContext tc, int on, float max_dist);
 void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int nframes, int ncols, int nrows,
                       KLT_FeatureList fl, KLT_FeatureTable ft, int ft_col);
 
+/* The reference harness loop with REPLACE (example3.c:54-76) in one call,
+   lost features replaced after every `every`-th tracked frame:
+     for (i = 1; i < nframes; i++) {
+       KLTTrackFeatures(tc, frames[i-1], frames[i], ncols, nrows, fl);
+       if (i % every == 0) KLTReplaceLostFeatures(tc, frames[i], ncols, nrows, fl);
+       if (ft) KLTStoreFeatureList(fl, ft, ft_col + i - 1);
+     }                                     every == 1: example3.c with REPLACE
+   The list (the aff_* fields of replaced slots included), the table, the kept
+   pyramid and the kernel cache end exactly as that loop leaves them.  It runs
+   on KLTTrackSequence's batched path with klt_hip_set_frames_replace on (off
+   again when the call returns): only the tracker launch is cut at the
+   replacement frames, where the list comes to the host for the selection.
+   every < 1 is a KLTError; the other argument checks are KLTTrackSequence's.  A
+   negative tc->mindist gets the reference's warning once and is set to 0.
+   It runs exactly the loop above where KLTTrackSequence would fall back to
+   its loop, when tc->sequentialMode is off (KLTReplaceLostFeatures then reads
+   frames[i] through a selection image and the kernel cache), and when
+   tc->affineConsistencyCheck >= 0; with every > nframes - 1 it is
+   KLTTrackSequence. */
+void KLTTrackSequenceReplace(KLT_TrackingContext tc, KLT_PixelType **frames, int nframes, int ncols, int nrows,
+                             KLT_FeatureList fl, KLT_FeatureTable ft, int ft_col, int every);
+
 /* KLTTrackSequence for nseq independent sequences of one geometry (a stereo
    rig, a camera array, many clips) in one call:
      for (s = 0; s < nseq; s++)

@@ -156,7 +156,9 @@ int klt_hip_set_track_merge(klt_hip_ctx *ctx, int on);
    lighting-insensitive, the generic pyramid path, per-call tracking) builds it.  A later
    reader of the kept pyramid that needs level-0 gradients (a call in another
    layout, klt_hip_frames_end_slot, klt_hip_min_eigen_rows) first completes
-   that one frame.  Results do not depend on it.  klt_hip_ctx_reset restores 1. */
+   that one frame (a replacement inside the call, klt_hip_set_frames_replace,
+   reads the image plane directly where k_min_eigen7_img applies).  Results do
+   not depend on it.  klt_hip_ctx_reset restores 1. */
 int klt_hip_set_lazy_grad(klt_hip_ctx *ctx, int on);
 /* Forward-backward (FB) consistency check, off by default.  With it on, every
    tracked frame img1 -> img2 of klt_hip_track (host or device arrays),
@@ -576,6 +578,69 @@ int klt_hip_min_eigen(klt_hip_ctx *ctx, int slot, const klt_hip_select_desc *des
    rows' windows reach rows a band-built pyramid does not hold. */
 int klt_hip_min_eigen_rows(klt_hip_ctx *ctx, const klt_hip_select_desc *desc, int row_lo, int row_hi, int *dev_map,
                            int *nx, int *ny, int *r0, int *r1);
+
+/* test hook: the trackability map of a level-0 image plane in device memory
+   (dev_img: ncols x nrows floats, tight rows -- what an image-only bank frame
+   of klt_hip_set_lazy_grad holds) into dev_map (nx * ny ints), by
+   k_min_eigen7_img: the kernel forms the gradients of each tile itself, with
+   the default gradient taps (sigma 1.0), bit for bit what the pyramid kernels
+   store, and then sums as the 7x7 map kernel does.  Synchronous.  Returns -1
+   with a message for a window other than 7x7, a step (nSkippedPixels + 1)
+   outside 1..2, or a border smaller than the window's half size. */
+int klt_hip_min_eigen_plane(klt_hip_ctx *ctx, const float *dev_img, int ncols, int nrows,
+                            const klt_hip_select_desc *desc, int *dev_map);
+/* the trackability-map kernel the context launched last, as rocprofv3 names it
+   (e.g. "kltdev::(anonymous namespace)::k_min_eigen7_img<1>"); "" before any
+   launch and after klt_hip_ctx_reset */
+const char *klt_hip_eigen_kernel(klt_hip_ctx *ctx);
+
+/* Replacement of lost features inside the device-resident batched calls, off
+   by default.  While it is on, klt_hip_track_frames and
+   klt_hip_track_frames_host do, after every tracked frame whose 1-based count
+   since the setting was turned on is a multiple of `every` and before the
+   next frame is tracked, what KLTReplaceLostFeatures does to the list in
+   sequential mode (selectGoodFeatures.c:514-541, :342-348): nothing when no
+   slot is lost (val < 0); otherwise the lost slots are filled from the
+   trackability map of the frame just tracked (klt_hip_select_dev_map with
+   overwrite_all 0; slots it cannot fill become (-1, -1, KLT_NOT_FOUND)).
+   Table row f and the `rows` callback carry the list after the replacement.
+   The result is, bit for bit, that of the loop
+       track frame; if (count % every == 0) replace; store
+   and does not depend on chunk, on how the frames are split over calls (the
+   count runs on from call to call) or on any tuning hook.
+   Only the tracker launch is cut at the replacement frames: a sub-launch
+   tracks frames [a, b) of a bank; the pyramid launches keep the call's chunk,
+   and the next chunk's pyramids are queued before the host waits for the
+   list.  The call runs on the context's stream (klt_hip_set_frames_overlap is
+   ignored while the setting is on).  The map reads the frame where it lies in
+   its bank: an image-only level 0 (klt_hip_set_lazy_grad) with a 7x7 window
+   and step <= 2 by k_min_eigen7_img, records or planes by the kernels
+   klt_hip_min_eigen_rows launches; an image-only frame with any other window
+   or step is completed first.  A replacement that filled a slot drops the
+   cached processing order.  A replacement due at the last frame of a call is
+   run.  The forward-backward check composes with it (a rejected feature is
+   lost and gets replaced; klt_hip_set_fb_table rows are unchanged).
+   Failing with -1 and a message before any launch, arrays untouched, while it
+   is on: klt_hip_track_frames_band, klt_hip_track_frames_multi,
+   klt_hip_track_sequence, and any call with klt_hip_set_frames_affine on.
+   klt_hip_set_frames_replace(NULL) turns it off, and so does
+   klt_hip_ctx_reset; turning it on zeroes the three counters of
+   klt_hip_get_frames_replace (frames tracked, replacements run -- those with
+   a lost slot --, slots filled; any pointer may be NULL) and the marks of
+   klt_hip_frames_replace_changed.  It returns -1, settings unchanged, for
+   every < 1, a border smaller than the window's half size, a window smaller
+   than 1, or a negative nSkippedPixels. */
+typedef struct {
+  klt_hip_select_desc sel;     /* window, borders (already max'ed), nSkippedPixels */
+  int mindist, min_eigenvalue; /* as in the tracking context */
+  int every;                   /* >= 1 */
+} klt_hip_replace_desc;
+int klt_hip_set_frames_replace(klt_hip_ctx *ctx, const klt_hip_replace_desc *desc);
+int klt_hip_get_frames_replace(klt_hip_ctx *ctx, int *on, long *frames, long *replacements, long *filled);
+/* changed[k] = 1 for every slot k < n a replacement has written (a new
+   feature or NOT_FOUND) since the setting was turned on, else 0: the slots
+   whose affine fields a klt.h caller resets (KLTTrackSequenceReplace) */
+int klt_hip_frames_replace_changed(klt_hip_ctx *ctx, unsigned char *changed, int n);
 
 /* the host half of KLTReplaceLostFeatures (selectGoodFeatures.c:514-541 ->
    _KLTSelectGoodFeatures' sort and minimum-distance fill, :425-453) over a

@@ -114,6 +114,8 @@ KLT_PROTOS = {
 # libklt_amd.so extensions of the klt.h surface (include/klt_amd.h)
 AMD_KLT_PROTOS = {
     "KLTTrackSequence": (None, [TC, C.POINTER(U8P), C.c_int, C.c_int, C.c_int, FL, FT, C.c_int]),
+    # ..., ft_col, every
+    "KLTTrackSequenceReplace": (None, [TC, C.POINTER(U8P), C.c_int, C.c_int, C.c_int, FL, FT, C.c_int, C.c_int]),
     # frames[s][f]; fl[s]; ft: NULL or ft[s] (each may be NULL)
     "KLTTrackSequences": (None, [TC, C.POINTER(C.POINTER(U8P)), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FL),
                                  C.POINTER(FT), C.c_int]),

@@ -208,6 +208,10 @@ static void taps_make(float sigma, klt_hip_taps *gauss, klt_hip_taps *deriv)
   }
 }
 
+/* the gradient kernels of the default grad_sigma (klt.c:27), for
+   klt_hip_min_eigen_plane: not through the cache */
+void klt_default_grad_taps(klt_hip_taps *gauss, klt_hip_taps *deriv) { taps_make(1.0f, gauss, deriv); }
+
 /* cached lookup as _KLTComputeSmoothedImage / _KLTComputeGradients do it,
    on a given cache state (the global one, or a copy for a dry run) */
 static void taps_lookup_in(taps_state *st, float sigma, klt_hip_taps *gauss, klt_hip_taps *deriv)
@@ -1012,8 +1016,10 @@ static void store_rows(void *user, int frame0, int nframes, int f0, int f1, cons
 
 #define SEQ_CHUNK 16 /* frames per upload / pyramid / tracking chunk of KLTTrackSequence */
 
-EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int nframes, int ncols, int nrows,
-                             KLT_FeatureList fl, KLT_FeatureTable ft, int ft_col)
+/* every == 0: KLTTrackSequence; every >= 1: KLTTrackSequenceReplace, the same
+   call with KLTReplaceLostFeatures after every `every`-th tracked frame */
+static void track_sequence(KLT_TrackingContext tc, KLT_PixelType **frames, int nframes, int ncols, int nrows,
+                           KLT_FeatureList fl, KLT_FeatureTable ft, int ft_col, int every)
 {
   klt_ctx_full *f = FULL(tc);
   klt_hip_ctx *dev;
@@ -1029,6 +1035,7 @@ EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int
   int *hv;
 
   if (nframes < 2) return;
+  if (every > T) every = 0; /* no replacement falls inside the sequence */
   window_fix(tc, NULL);
   affine_check_tc(tc);
   if (ft && (ft_col < 0 || ft_col + T > ft->nFrames))
@@ -1037,7 +1044,7 @@ EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int
   if (ft && ft->nFeatures != n)
     KLTError("(KLTStoreFeatures) FeatureList and FeatureTable must have the same number of features");
   dev = device_of(tc);
-  apply_fb(tc, "KLTTrackSequence");
+  apply_fb(tc, every ? "KLTTrackSequenceReplace" : "KLTTrackSequence");
   seq_start = tc->sequentialMode && tc->pyramid_last != NULL && f->last_slot >= 0;
   if (seq_start && (f->last_w != ncols || f->last_h != nrows))
     KLTError("(KLTTrackSequence) Size of incoming image (%d by %d) is different from size of "
@@ -1057,17 +1064,31 @@ EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int
   pyr_desc_in(&st, tc, ncols, nrows, tc->nPyramidLevels, 1, &e2);
   steady = taps_state_eq(&st, &after1) && !memcmp(&e2, &d2, sizeof d2) &&
            (tc->sequentialMode || !memcmp(&e1, &d2, sizeof d2)) && !tc->writeInternalImages;
+  /* the batched replacement reads the tracked frame's own pyramid, which is
+     KLTReplaceLostFeatures in sequential mode only (otherwise it builds a
+     selection image of frames[i] through the kernel cache), and does not
+     combine with the affine check */
+  if (every && (!tc->sequentialMode || affine)) steady = 0;
   if (!steady) {
     for (i = 1; i < nframes; i++) {
       KLTTrackFeatures(tc, frames[i - 1], frames[i], ncols, nrows, fl);
+      if (every && i % every == 0) KLTReplaceLostFeatures(tc, frames[i], ncols, nrows, fl);
       if (ft) KLTStoreFeatureList(fl, ft, ft_col + i - 1);
     }
     return;
   }
   if (KLT_verbose >= 1) {
-    fprintf(stderr, "(KLT) Tracking %d features through %d %d by %d frames...  ", KLTCountRemainingFeatures(fl),
-            T, ncols, nrows);
+    fprintf(stderr, "(KLT) Tracking %d features through %d %d by %d frames", KLTCountRemainingFeatures(fl), T, ncols,
+            nrows);
+    if (every) fprintf(stderr, ", replacing lost features every %d", every);
+    fprintf(stderr, "...  ");
     fflush(stderr);
+  }
+  if (every && tc->mindist < 0) {
+    KLTWarning("(_KLTSelectGoodFeatures) Tracking context field tc->mindist is negative (%d); "
+               "setting to zero",
+               tc->mindist);
+    tc->mindist = 0;
   }
 
   /* where the first tracked frame starts from: the kept pyramid (sequential
@@ -1115,6 +1136,40 @@ EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int
     dev_check(tc, rc, "sequence tracking");
     dev_check(tc, klt_hip_affine_state_get(dev, aio.aff, aio.state, n), "affine state download");
     affine_end(tc, fl, hx, hy, hv, &aio);
+  } else if (every) {
+    /* KLTReplaceLostFeatures inside the batched call (klt_hip_set_frames_replace) */
+    klt_hip_replace_desc rd;
+    unsigned char *changed = (unsigned char *)malloc((size_t)n + 1), *skip = (unsigned char *)malloc((size_t)n + 1);
+    int rc;
+    if (!changed || !skip) KLTError("(KLTTrackSequenceReplace) Out of memory");
+    rd.sel.window_width = tc->window_width;
+    rd.sel.window_height = tc->window_height;
+    rd.sel.borderx = tc->borderx < tc->window_width / 2 ? tc->window_width / 2 : tc->borderx;
+    rd.sel.bordery = tc->bordery < tc->window_height / 2 ? tc->window_height / 2 : tc->bordery;
+    rd.sel.nSkippedPixels = tc->nSkippedPixels;
+    rd.mindist = tc->mindist;
+    rd.min_eigenvalue = tc->min_eigenvalue;
+    rd.every = every;
+    dev_check(tc, klt_hip_set_frames_replace(dev, &rd), "replacement setting");
+    rc = klt_hip_track_frames_host(dev, &d2, &td, src, seed_first ? nframes : nframes - 1, seed_first, SEQ_CHUNK, hx,
+                                   hy, hv, n, ft ? store_rows : NULL, &sr);
+    if (rc == 0) rc = klt_hip_frames_replace_changed(dev, changed, n);
+    klt_hip_set_frames_replace(dev, NULL); /* off again, whatever the call returned */
+    dev_check(tc, rc, "sequence tracking");
+    /* a slot lost on entry that no replacement wrote stays untouched (:1346);
+       a written one got mark_found's treatment when it was written */
+    for (k = 0; k < n; k++) skip[k] = fl->feature[k]->val < 0 && !changed[k];
+    klt_select_apply(fl, hx, hy, hv, changed);
+    for (k = 0; k < n; k++) {
+      KLT_Feature ftr = fl->feature[k];
+      if (skip[k]) continue;
+      ftr->x = hx[k];
+      ftr->y = hy[k];
+      ftr->val = hv[k];
+      if (hv[k] != KLT_TRACKED) drop_affine(ftr);
+    }
+    free(changed);
+    free(skip);
   } else {
     dev_check(tc, klt_hip_track_frames_host(dev, &d2, &td, src, seed_first ? nframes : nframes - 1, seed_first,
                                             SEQ_CHUNK, hx, hy, hv, n, ft ? store_rows : NULL, &sr),
@@ -1151,6 +1206,21 @@ EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int
     fprintf(stderr, "\n\t%d features successfully tracked.\n", KLTCountRemainingFeatures(fl));
     fflush(stderr);
   }
+}
+
+EXPORT void KLTTrackSequence(KLT_TrackingContext tc, KLT_PixelType **frames, int nframes, int ncols, int nrows,
+                             KLT_FeatureList fl, KLT_FeatureTable ft, int ft_col)
+{
+  track_sequence(tc, frames, nframes, ncols, nrows, fl, ft, ft_col, 0);
+}
+
+/* the example3.c loop with REPLACE, KLTReplaceLostFeatures after every
+   `every`-th tracked frame (klt_amd.h) */
+EXPORT void KLTTrackSequenceReplace(KLT_TrackingContext tc, KLT_PixelType **frames, int nframes, int ncols, int nrows,
+                                    KLT_FeatureList fl, KLT_FeatureTable ft, int ft_col, int every)
+{
+  if (every < 1) KLTError("(KLTTrackSequenceReplace) every=%d: expected at least 1", every);
+  track_sequence(tc, frames, nframes, ncols, nrows, fl, ft, ft_col, every);
 }
 
 /* ------------------------------------------------------------------ */

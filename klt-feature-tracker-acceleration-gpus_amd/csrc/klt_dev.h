@@ -259,9 +259,19 @@ hipError_t launch_cols(hipStream_t st, const float *in, int W, int H, const RTap
 hipError_t launch_subsample(hipStream_t st, const float *in, int W, int ss, float *out, int W1, int H1);
 // trackability map over the nx x ny grid from (bx, by), step apart; ps: the
 // gradients' pixel stride (1 planes; 3 an interleaved level's {gx, gy, img}
-// records, gx = base + kRecGx, gy = base + kRecGy)
+// records, gx = base + kRecGx, gy = base + kRecGy); name: out, the kernel
+// instance launched, as rocprofv3 names it
 hipError_t launch_min_eigen(hipStream_t st, const float *gx, const float *gy, int W, int ps, int bx, int by, int step,
-                            int nx, int ny, int hw, int hh, int *out);
+                            int nx, int ny, int hw, int hh, int *out, const char **name = nullptr);
+// the same map (7x7 window, step 1 or 2) from a level-0 img plane alone, row
+// stride W: k_min_eigen7_img forms the gradients of its tile with the 7-tap
+// gradient kernels t (reversed, as k_rows / k_cols take them), bit for bit
+// what launch_rows / launch_cols over the whole plane give
+struct GradTaps {
+  float g[2 * kRG + 1], d[2 * kRG + 1];  // gauss, derivative
+};
+hipError_t launch_min_eigen_img(hipStream_t st, const float *img, int W, int H, const GradTaps &t, int bx, int by,
+                                int step, int nx, int ny, int *out, const char **name = nullptr);
 hipError_t launch_synth(hipStream_t st, unsigned long long seed, int t0, int n, int W, int H, int row0, uint8_t *out,
                         long pitch, long fstride);
 hipError_t launch_selftest_sqrt(const double *in, double *out, int n);

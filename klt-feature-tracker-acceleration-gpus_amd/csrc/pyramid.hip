@@ -5,7 +5,8 @@
 //                          convolve.c:37-53,273-314; pyramid.c:87-131)
 //   k_u8_to_f32 / k_rows / k_cols / k_subsample   the generic path (any sigma,
 //                         levels, subsampling), one 1-D pass per launch
-//   k_min_eigen           the trackability map (selectGoodFeatures.c:375-424)
+//   k_min_eigen           the trackability map (selectGoodFeatures.c:375-424);
+//   k_min_eigen7_img      the same from a level-0 img plane alone
 //   k_synth               synthetic frames (include/klt_synth.h)
 //
 // Parity contract: every output is bit-identical to the reference CPU path
@@ -901,39 +902,14 @@ constexpr int kMaxStep = 2;
 static_assert(RPW % 2 == 0, "grid rows in pairs");
 }  // namespace eig
 
-// STEP: the grid step (1 or 2), so that the LDS tile is sized for it (24.6 KB
-// at step 1: six workgroups per CU)
+// The window sums of a staged tile and the map values, for the workgroup's
+// 64 x 16 grid points from (ix0, iy0): gq / gm hold the products of the R x C
+// cells (C = (TX - 1) STEP + WIN per row).  After the barrier that ends the staging.
 template <int STEP>
-__global__ __launch_bounds__(256) void k_min_eigen7(const float *__restrict__ gx, const float *__restrict__ gy, int W,
-                                                   int ps, int bx, int by, int nx, int ny, int *__restrict__ out) {
+__device__ __forceinline__ void eig_tile_sums(const f2 *gq, const float *gm, int ix0, int iy0, int nx, int ny,
+                                              int *__restrict__ out) {
   using namespace eig;
-  constexpr int step = STEP, C = (TX - 1) * STEP + WIN, R = (TY - 1) * STEP + WIN, C_MAX = C;
-  // per cell {gx*gx, gy*gy} and gx*gy: 12 bytes, 18.5 KB at step 1, so that a
-  // CU holds eight workgroups and a 1080p map's 2 040 tiles run in one round
-  // (16-byte cells: six per CU, and a third of the tiles in a second round)
-  __shared__ f2 gq[R * C];
-  __shared__ float gm[R * C];
-  const int tiles_x = (nx + TX - 1) / TX;
-  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
-  const int ix0 = tx * TX, iy0 = ty * TY;
-  // pixel (x0 + c, y0 + r) for LDS cell (r, c); clamped to the last grid
-  // point's window (tiles past nx / ny read valid pixels they never use)
-  const int x0 = bx + ix0 * step - HW, y0 = by + iy0 * step - HW;
-  const int xmax = bx + (nx - 1) * step + HW, ymax = by + (ny - 1) * step + HW;
-#pragma unroll
-  for (int p0 = 0; p0 < R * C; p0 += 256) {  // a compile-time trip count: the loads issue together
-    const int p = p0 + (int)threadIdx.x;
-    if (p >= R * C) break;
-    const int r = p / C, c = p - r * C;
-    const int yy = min(y0 + r, ymax), xx = min(x0 + c, xmax);
-    const long o = ((long)yy * W + xx) * ps;
-    const float a = gx[o], b = gy[o];
-    const f2 ab = {a, b};
-    const f2 sq = ab * ab;
-    gq[r * C_MAX + c] = sq;
-    gm[r * C_MAX + c] = a * b;
-  }
-  __syncthreads();
+  constexpr int step = STEP, C_MAX = (TX - 1) * STEP + WIN;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int ix = ix0 + lane;
   if (ix >= nx) return;
@@ -973,6 +949,133 @@ __global__ __launch_bounds__(256) void k_min_eigen7(const float *__restrict__ gx
     finish(qa, xa, iy);
     if (iy + 1 < ny) finish(qb, xb, iy + 1);
   }
+}
+
+// STEP: the grid step (1 or 2), so that the LDS tile is sized for it (24.6 KB
+// at step 1: six workgroups per CU)
+template <int STEP>
+__global__ __launch_bounds__(256) void k_min_eigen7(const float *__restrict__ gx, const float *__restrict__ gy, int W,
+                                                   int ps, int bx, int by, int nx, int ny, int *__restrict__ out) {
+  using namespace eig;
+  constexpr int step = STEP, C = (TX - 1) * STEP + WIN, R = (TY - 1) * STEP + WIN, C_MAX = C;
+  // per cell {gx*gx, gy*gy} and gx*gy: 12 bytes, 18.5 KB at step 1, so that a
+  // CU holds eight workgroups and a 1080p map's 2 040 tiles run in one round
+  // (16-byte cells: six per CU, and a third of the tiles in a second round)
+  __shared__ f2 gq[R * C];
+  __shared__ float gm[R * C];
+  const int tiles_x = (nx + TX - 1) / TX;
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int ix0 = tx * TX, iy0 = ty * TY;
+  // pixel (x0 + c, y0 + r) for LDS cell (r, c); clamped to the last grid
+  // point's window (tiles past nx / ny read valid pixels they never use)
+  const int x0 = bx + ix0 * step - HW, y0 = by + iy0 * step - HW;
+  const int xmax = bx + (nx - 1) * step + HW, ymax = by + (ny - 1) * step + HW;
+#pragma unroll
+  for (int p0 = 0; p0 < R * C; p0 += 256) {  // a compile-time trip count: the loads issue together
+    const int p = p0 + (int)threadIdx.x;
+    if (p >= R * C) break;
+    const int r = p / C, c = p - r * C;
+    const int yy = min(y0 + r, ymax), xx = min(x0 + c, xmax);
+    const long o = ((long)yy * W + xx) * ps;
+    const float a = gx[o], b = gy[o];
+    const f2 ab = {a, b};
+    const f2 sq = ab * ab;
+    gq[r * C_MAX + c] = sq;
+    gm[r * C_MAX + c] = a * b;
+  }
+  __syncthreads();
+  eig_tile_sums<STEP>(gq, gm, ix0, iy0, nx, ny, out);
+}
+
+// The same map from a level-0 img plane alone (row stride W): what an
+// image-only bank frame holds (klt_hip_set_lazy_grad).  The workgroup stages
+// its image tile with a halo of kRG (gradient) + HW (window) pixels, forms
+// gx = cols(rows(img, d), g) and gy = cols(rows(img, g), d) for its R x C
+// cells in LDS -- k_rows' and k_cols' tap order from +0, one rounding per
+// operation, and their border rule: a 1-D pass leaves its outer kRG columns
+// (rows) at zero and the second pass reads those zeros, so a gradient is zero
+// within kRG pixels of any image edge -- and goes on as k_min_eigen7 does:
+// the same bits as that kernel over the completed frame.
+// LDS: the rows pass {tx, ty} per cell of R + 2 kRG rows, which the products
+// {gx*gx, gy*gy} then overwrite (every gradient of the tile is in registers
+// by then), and the image tile, which gx*gy overwrites: 24.2 KB at step 1
+// (six workgroups per CU), 69.7 KB at step 2 (two).
+template <int STEP>
+__global__ __launch_bounds__(256) void k_min_eigen7_img(const float *__restrict__ img, int W, int H, GradTaps t,
+                                                       int bx, int by, int nx, int ny, int *__restrict__ out) {
+  using namespace eig;
+  constexpr int step = STEP, C = (TX - 1) * STEP + WIN, R = (TY - 1) * STEP + WIN;
+  constexpr int G = kRG, NT = 2 * kRG + 1, CI = C + 2 * G, RI = R + 2 * G;
+  constexpr int NC = (R * C + 255) / 256;  // cells per thread
+  __shared__ f2 txy[RI * C];    // rows pass, then gq
+  __shared__ float im[RI * CI];  // image tile, then gm
+  static_assert(R * C <= RI * CI, "gm fits the image tile");
+  const int tiles_x = (nx + TX - 1) / TX;
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int ix0 = tx * TX, iy0 = ty * TY;
+  // pixel (x0 + c, y0 + r) for gradient cell (r, c); the image tile starts G
+  // pixels before it and is clamped to the image (a clamped value only feeds
+  // gradients the border rule sets to zero, or cells no window reads)
+  const int x0 = bx + ix0 * step - HW, y0 = by + iy0 * step - HW;
+#pragma unroll
+  for (int p0 = 0; p0 < RI * CI; p0 += 256) {
+    const int p = p0 + (int)threadIdx.x;
+    if (p >= RI * CI) break;
+    const int r = p / CI, c = p - r * CI;
+    const int yy = clampi(y0 - G + r, 0, H - 1), xx = clampi(x0 - G + c, 0, W - 1);
+    im[p] = img[(long)yy * W + xx];
+  }
+  __syncthreads();
+  // rows pass (k_rows): tx = rows(img, d), ty = rows(img, g)
+#pragma unroll 1
+  for (int p = (int)threadIdx.x; p < RI * C; p += 256) {
+    const int r = p / C, c = p - r * C, x = x0 + c;
+    float a = 0.0f, b = 0.0f;
+    if (x >= G && x < W - G) {
+      const float *q = im + r * CI + c;  // pixels x - G .. x + G
+#pragma unroll
+      for (int m = 0; m < NT; ++m) {
+        a += q[m] * t.d[m];
+        b += q[m] * t.g[m];
+      }
+    }
+    txy[p] = f2{a, b};
+  }
+  __syncthreads();
+  // columns pass (k_cols): gx = cols(tx, g), gy = cols(ty, d)
+  float vx[NC], vy[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    const int p = k * 256 + (int)threadIdx.x;
+    float a = 0.0f, b = 0.0f;
+    if (p < R * C) {
+      const int r = p / C, c = p - r * C, y = y0 + r;
+      if (y >= G && y < H - G) {
+#pragma unroll
+        for (int m = 0; m < NT; ++m) {
+          const f2 v = txy[(r + m) * C + c];  // rows y - G .. y + G
+          a += v.x * t.g[m];
+          b += v.y * t.d[m];
+        }
+      }
+    }
+    vx[k] = a;
+    vy[k] = b;
+  }
+  __syncthreads();
+  f2 *gq = txy;
+  float *gm = im;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    const int p = k * 256 + (int)threadIdx.x;
+    if (p < R * C) {
+      const f2 ab = {vx[k], vy[k]};
+      gq[p] = ab * ab;
+      gm[p] = vx[k] * vy[k];
+    }
+  }
+  __syncthreads();
+  eig_tile_sums<STEP>(gq, gm, ix0, iy0, nx, ny, out);
 }
 
 // synthetic frames (include/klt_synth.h), one thread per pixel
@@ -1138,10 +1241,15 @@ hipError_t launch_subsample(hipStream_t st, const float *in, int W, int ss, floa
 }
 
 hipError_t launch_min_eigen(hipStream_t st, const float *gx, const float *gy, int W, int ps, int bx, int by, int step,
-                            int nx, int ny, int hw, int hh, int *out) {
+                            int nx, int ny, int hw, int hh, int *out, const char **name) {
   const long np = (long)nx * ny;
   if (np == 0) return hipSuccess;
-  if (hw == eig::HW && hh == eig::HW && step >= 1 && step <= eig::kMaxStep) {
+  const bool win7 = hw == eig::HW && hh == eig::HW && step >= 1 && step <= eig::kMaxStep;
+  if (name)
+    *name = !win7       ? "kltdev::(anonymous namespace)::k_min_eigen"
+            : step == 1 ? "kltdev::(anonymous namespace)::k_min_eigen7<1>"
+                        : "kltdev::(anonymous namespace)::k_min_eigen7<2>";
+  if (win7) {
     const long tiles = (long)((nx + eig::TX - 1) / eig::TX) * ((ny + eig::TY - 1) / eig::TY);
     if (step == 1)
       hipLaunchKernelGGL(k_min_eigen7<1>, dim3((unsigned)tiles), dim3(256), 0, st, gx, gy, W, ps, bx, by, nx, ny, out);
@@ -1151,6 +1259,21 @@ hipError_t launch_min_eigen(hipStream_t st, const float *gx, const float *gy, in
   }
   hipLaunchKernelGGL(k_min_eigen, dim3(blocks_for(np)), dim3(kBlock), 0, st, gx, gy, W, ps, bx, by, step, nx, ny, hw,
                      hh, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_min_eigen_img(hipStream_t st, const float *img, int W, int H, const GradTaps &t, int bx, int by,
+                                int step, int nx, int ny, int *out, const char **name) {
+  if ((long)nx * ny == 0) return hipSuccess;
+  if (step < 1 || step > eig::kMaxStep || W < 1 || H < 1) return hipErrorInvalidValue;
+  if (name)
+    *name = step == 1 ? "kltdev::(anonymous namespace)::k_min_eigen7_img<1>"
+                      : "kltdev::(anonymous namespace)::k_min_eigen7_img<2>";
+  const long tiles = (long)((nx + eig::TX - 1) / eig::TX) * ((ny + eig::TY - 1) / eig::TY);
+  if (step == 1)
+    hipLaunchKernelGGL(k_min_eigen7_img<1>, dim3((unsigned)tiles), dim3(256), 0, st, img, W, H, t, bx, by, nx, ny, out);
+  else
+    hipLaunchKernelGGL(k_min_eigen7_img<2>, dim3((unsigned)tiles), dim3(256), 0, st, img, W, H, t, bx, by, nx, ny, out);
   return hipGetLastError();
 }
 

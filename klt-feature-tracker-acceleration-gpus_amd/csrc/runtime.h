@@ -182,6 +182,19 @@ struct __attribute__((visibility("default"))) klt_hip_ctx {  // its constructor 
   int *aff_stab = nullptr;
   long aff_tab_stride = 0;
   int aff_fresh = 1, aff_depth = 0;
+  // replacement of lost features inside the batched calls
+  // (klt_hip_set_frames_replace): the counters since it was turned on, the
+  // slots a replacement has written, the map and the pinned list (x | y | val)
+  int rep_on = 0;
+  klt_hip_replace_desc rep{};
+  long rep_frames = 0, rep_runs = 0, rep_filled = 0;
+  std::vector<unsigned char> rep_changed;
+  int *d_rep_map = nullptr;
+  size_t rep_map_cap = 0;
+  float *h_rep = nullptr;
+  size_t h_rep_cap = 0;  // features
+  hipEvent_t ev_rep = nullptr;
+  const char *eig_kernel = nullptr;  // instance name of the last map launch (klt_hip_eigen_kernel)
   // band calls: 1 = the next chunk's frames are ready when the call is made
   // (not written by work still queued on the tracking stream), so its
   // build-ahead waits for its bank and for this chunk's processing order

@@ -210,6 +210,9 @@ KLT_API void klt_hip_ctx_destroy(klt_hip_ctx *c) {
   hipFree(c->d_feat);
   if (c->h_feat) hipHostFree(c->h_feat);
   hipFree(c->d_eig);
+  hipFree(c->d_rep_map);
+  if (c->h_rep) hipHostFree(c->h_rep);
+  if (c->ev_rep) hipEventDestroy(c->ev_rep);
   sel_engine_destroy(c->sel);
   for (auto &r : c->registered) (void)hipHostUnregister(const_cast<unsigned char *>(r.first));
   for (void *p : {(void *)c->d_aff_store, (void *)c->d_aff, (void *)c->d_xp, (void *)c->d_yp, (void *)c->d_astage,
@@ -319,6 +322,10 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->aff_tab_stride = 0;
   c->aff_fresh = 1;
   c->aff_depth = 0;
+  c->rep_on = 0;
+  c->rep_frames = c->rep_runs = c->rep_filled = 0;
+  c->rep_changed.clear();
+  c->eig_kernel = nullptr;
   c->frames_sched = kSchedOne;
   c->tail_left = kTailLeftDefault;
   c->wave_t = nullptr;
@@ -346,6 +353,8 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
 KLT_API const char *klt_hip_last_error(klt_hip_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
 KLT_API const char *klt_hip_track_kernel(klt_hip_ctx *c) { return c && c->track_kernel ? c->track_kernel : ""; }
+
+KLT_API const char *klt_hip_eigen_kernel(klt_hip_ctx *c) { return c && c->eig_kernel ? c->eig_kernel : ""; }
 
 KLT_API int klt_hip_set_stream(klt_hip_ctx *c, void *stream) {
   if (!c) return -1;
@@ -705,7 +714,8 @@ KLT_API int klt_hip_min_eigen(klt_hip_ctx *c, int s, const klt_hip_select_desc *
   {
     TimedScope ts(c, T_EIG, c->stream);
     if (launched(c, "k_min_eigen", launch_min_eigen(c->stream, L.il ? L.img + kRecGx : L.gx, L.il ? L.img + kRecGy : L.gy,
-                                                    L.w, L.il ? 3 : 1, bx, by, step, gx, gy, hw, hh, c->d_eig)))
+                                                    L.w, L.il ? 3 : 1, bx, by, step, gx, gy, hw, hh, c->d_eig,
+                                                    &c->eig_kernel)))
       return -1;
   }
   HIPCHK(c, hipMemcpyAsync(vals, c->d_eig, sizeof(int) * np, hipMemcpyDeviceToHost, c->stream));
@@ -724,7 +734,7 @@ static int eigen_to_dev(klt_hip_ctx *c, int s, const klt_hip_select_desc *d, int
   return launched(c, "k_min_eigen", launch_min_eigen(c->stream, L.il ? L.img + kRecGx : L.gx, L.il ? L.img + kRecGy : L.gy,
                                                      L.w, L.il ? 3 : 1, d->borderx, d->bordery,
                                                      d->nSkippedPixels + 1, *nx, *ny, d->window_width / 2,
-                                                     d->window_height / 2, c->d_eig));
+                                                     d->window_height / 2, c->d_eig, &c->eig_kernel));
 }
 
 static SelEngine *sel_of(klt_hip_ctx *c) {

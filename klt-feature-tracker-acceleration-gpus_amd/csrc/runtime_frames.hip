@@ -287,6 +287,9 @@ int frames_check(klt_hip_ctx *c, const FramesCall &q, int chunk) {
   if (ntab && q.tab_stride < n) return fail(c, "track_frames: table stride %ld < n %d", q.tab_stride, n);
   if (q.pitch < pd->ncols) return fail(c, "track_frames: pitch %ld < ncols %d", q.pitch, pd->ncols);
   if (check_window(c, q.td)) return -1;
+  if (c->rep_on && c->aff_on)
+    return fail(c, "track_frames: the affine check does not combine with the replacement of lost features "
+                "(klt_hip_set_frames_affine, klt_hip_set_frames_replace)");
   if (track_refused(c, q.td, q.band != nullptr, n, q.band ? "track_frames_band" : "track_frames")) return -1;
   const TrkLevel p0 = prev_level(c, 0);
   const int nl = c->prev.bank < 0 ? c->slot[c->prev.slot].nlev : c->bank[c->prev.bank].nlev;
@@ -388,6 +391,7 @@ int plan_frames(klt_hip_ctx *c, const FramesCall &q, int chunk, FramesPlan &p) {
   constexpr int kAutoLazy = kSchedTail;
   p.sched = env_frames_sched() >= 0 ? env_frames_sched() : c->frames_sched;
   if (p.sched == kSchedAuto) p.sched = p.lazy ? kAutoLazy : kSchedBeside;
+  if (c->rep_on) p.sched = kSchedOne;  // replacement inside the call: the context's stream alone
   p.serial = band ? false : (p.sched == kSchedOne || q.nframes <= chunk);
   p.tail = !band && !p.serial && p.sched == kSchedTail;
   p.tail_left = (unsigned)(env_frames_tail() >= 0 ? env_frames_tail() : c->tail_left);
@@ -492,14 +496,17 @@ int build_chunk(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, int bi
 
 // the chunk's tracker launch (b: its processing order, already queued); the
 // chunk's last frame is the kept pyramid from here on.  rel: out, the exit
-// count at which the pyramid stream may start the next build
+// count at which the pyramid stream may start the next build.
+// f0 > 0 (replacement inside the call): a sub-launch over the bank's frames
+// [f0, f0 + F), the call's frames from j0 on; the kept pyramid it starts from
+// is the bank's frame f0 - 1, where the sub-launch before it ended
 int launch_chunk(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, int bi, int j0, int F, TrkArgs &a,
-                 TrkFramesArgs &b, TailRelease &rel) {
+                 TrkFramesArgs &b, TailRelease &rel, int f0 = 0) {
   const BandSpec *band = q.band;
   const Bank &K = c->bank[bi];
   for (int l = 0; l < q.pd->nlevels; ++l) {
     a.A[l] = prev_level(c, l);
-    a.B[l] = level_view(K.lv[l], 0, p.fz ? K.vlo[l] : 0, p.fz ? K.vhi[l] : (1 << 30));
+    a.B[l] = level_view(K.lv[l], f0, p.fz ? K.vlo[l] : 0, p.fz ? K.vhi[l] : (1 << 30));
     b.lfs[l] = (long)K.lv[l].w * K.lv[l].h * (K.lv[l].il == kLayoutRec ? 3 : 1);
   }
   b.nframes = F;
@@ -520,7 +527,7 @@ int launch_chunk(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, int b
     return -1;
   HMARK_IN("track");
   if (!p.serial && !p.ahead && c->prev.bank >= 0) HIPCHK(c, hipEventRecord(c->ev_bfree[c->prev.bank], c->stream));
-  c->prev = PrevRef{bi, F - 1};
+  c->prev = PrevRef{bi, f0 + F - 1};
   return 0;
 }
 
@@ -549,6 +556,148 @@ int build_ahead(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, const 
   c->pre.row_lo = band->row_lo;
   c->pre.row_hi = band->row_hi;
   c->pre.il = p.bil;
+  return 0;
+}
+
+// the next bank in turn; one built ahead for a band call is taken or overwritten
+int take_bank(klt_hip_ctx *c) {
+  const int bi = c->bank_next;
+  c->bank_next = (bi + 1) % 3;
+  if (c->pre.bank == bi) c->pre.bank = -1;
+  return bi;
+}
+
+// One replacement of lost features (klt_hip_set_frames_replace): the kept
+// pyramid is the frame just tracked, `row` its table row.  The list comes to
+// the host (pinned, x | y | val); `ahead` queues whatever does not depend on
+// it before the host waits.  With a lost slot, the frame's trackability map
+// is taken where the frame lies -- an image-only level 0 by k_min_eigen7_img
+// when the window and step are its own, anything else as
+// klt_hip_min_eigen_rows does it (which completes an image-only frame first)
+// -- and the selection engine fills the slots; the list and its table row go
+// back to the device.
+template <class Ahead>
+int replace_lost(klt_hip_ctx *c, const FramesCall &q, long row, Ahead ahead) {
+  const int n = q.n;
+  if (n <= 0) return ahead();
+  hipStream_t st = c->stream;
+  if (c->h_rep_cap < (size_t)n || !c->h_rep) {
+    if (c->h_rep) {
+      HIPCHK(c, hipStreamSynchronize(st));  // no copy still uses the old block
+      HIPCHK(c, hipHostFree(c->h_rep));
+    }
+    c->h_rep = nullptr;
+    c->h_rep_cap = 0;
+    HIPCHK(c, hipHostMalloc((void **)&c->h_rep, 3 * sizeof(float) * (size_t)n, hipHostMallocDefault));
+    c->h_rep_cap = (size_t)n;
+  }
+  if (!c->ev_rep) HIPCHK(c, hipEventCreateWithFlags(&c->ev_rep, hipEventDisableTiming));
+  float *hx = c->h_rep, *hy = hx + n;
+  int *hv = reinterpret_cast<int *>(hy + n);
+  const size_t nb = sizeof(float) * (size_t)n;
+  HIPCHK(c, hipMemcpyAsync(hx, q.x, nb, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(hy, q.y, nb, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(hv, q.val, nb, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipEventRecord(c->ev_rep, st));
+  if (ahead()) return -1;
+  HIPCHK(c, hipEventSynchronize(c->ev_rep));
+  int lost = 0;
+  for (int k = 0; k < n; ++k) lost += hv[k] < 0;
+  if (!lost) return 0;  // KLTReplaceLostFeatures: nothing to replace
+  const klt_hip_select_desc &sd = c->rep.sel;
+  const TrkLevel L = prev_level(c, 0);
+  const int hw = sd.window_width / 2, hh = sd.window_height / 2, step = sd.nSkippedPixels + 1;
+  const int cx = L.w - 2 * sd.borderx, cy = L.h - 2 * sd.bordery;
+  int nx = cx > 0 ? (cx + step - 1) / step : 0, ny = cy > 0 ? (cy + step - 1) / step : 0;
+  if (grow(c, &c->d_rep_map, &c->rep_map_cap, (size_t)nx * ny)) return -1;
+  if ((long)nx * ny > 0) {
+    const bool img7 = L.il == kLayoutImg && hw == kRG && hh == kRG && step <= 2 && c->lazy_gg.w == 2 * kRG + 1 &&
+                      c->lazy_gd.w == 2 * kRG + 1;
+    if (img7) {
+      GradTaps t;
+      for (int m = 0; m < 2 * kRG + 1; ++m) {
+        t.g[m] = c->lazy_gg.k[m];
+        t.d[m] = c->lazy_gd.k[m];
+      }
+      TimedScope ts(c, T_EIG, st);
+      if (launched(c, "k_min_eigen7_img", launch_min_eigen_img(st, L.img, L.w, L.h, t, sd.borderx, sd.bordery, step, nx,
+                                                               ny, c->d_rep_map, &c->eig_kernel)))
+        return -1;
+    } else {
+      int r0 = 0, r1 = 0;
+      const int rc = klt_hip_min_eigen_rows(c, &sd, 0, L.h, c->d_rep_map, &nx, &ny, &r0, &r1);
+      if (rc < 0) return -1;
+      if (rc > 0 || r0 != 0 || r1 != ny) return fail(c, "track_frames: the tracked frame does not hold every row of the map");
+    }
+  }
+  std::vector<unsigned char> changed((size_t)n, 0);
+  if (klt_hip_select_dev_map(c, c->d_rep_map, nx, ny, &sd, L.w, L.h, c->rep.mindist, c->rep.min_eigenvalue, 0, hx, hy,
+                             hv, changed.data(), n))
+    return -1;
+  if (c->rep_changed.size() < (size_t)n) c->rep_changed.resize((size_t)n, 0);
+  long filled = 0, written = 0;
+  for (int k = 0; k < n; ++k) {
+    if (!changed[k]) continue;
+    c->rep_changed[k] = 1;
+    ++written;
+    filled += hv[k] >= 0;
+  }
+  ++c->rep_runs;
+  c->rep_filled += filled;
+  if (!written) return 0;
+  HIPCHK(c, hipMemcpyAsync(q.x, hx, nb, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(q.y, hy, nb, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(q.val, hv, nb, hipMemcpyHostToDevice, st));
+  if (q.tab_x) {  // the row carries the list after the replacement
+    HIPCHK(c, hipMemcpyAsync(q.tab_x + row * q.tab_stride, q.x, nb, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(q.tab_y + row * q.tab_stride, q.y, nb, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(q.tab_val + row * q.tab_stride, q.val, nb, hipMemcpyDeviceToDevice, st));
+  }
+  // results never depend on the cached processing order, but new features
+  // would sit in the lost features' places
+  if (filled) c->perm_n = -1;
+  return 0;
+}
+
+// The chunks of a call that replaces lost features: the pyramid launches keep
+// the chunk, the tracker launch is cut where the frame count since the setting
+// was turned on reaches a multiple of `every`, and each cut runs the
+// replacement.  All on the tracking stream; the next chunk's pyramids are
+// queued before the host waits for the list of a chunk's last frame.
+int track_frames_replacing(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, TrkArgs &a,
+                           PstreamBehind &behind) {
+  const int every = c->rep.every;
+  TailRelease rel{p.tail_left, false, 0};
+  int bi = -1, ahead_bank = -1;
+  for (int j0 = 0; j0 < q.nframes; j0 += p.F) {
+    const int F = p.F < q.nframes - j0 ? p.F : q.nframes - j0;
+    if (ahead_bank >= 0) {
+      bi = ahead_bank;
+    } else {
+      bi = take_bank(c);
+      if (build_chunk(c, q, p, bi, F, q.frames + (long)j0 * q.stride, c->stream, false, behind, rel)) return -1;
+    }
+    ahead_bank = -1;
+    const int jn = j0 + F, Fn = p.F < q.nframes - jn ? p.F : q.nframes - jn;
+    for (int f0 = 0; f0 < F;) {
+      const long due = every - c->rep_frames % every;  // frames up to the next replacement
+      const int f1 = f0 + due < F ? (int)(f0 + due) : F;
+      TrkFramesArgs b;
+      memset(&b, 0, sizeof b);
+      if (q.n > 0 && order_features(c, c->stream, q.pd->nrows, q.y, q.val, q.n, f1 - f0, nullptr, b)) return -1;
+      if (launch_chunk(c, q, p, bi, j0 + f0, f1 - f0, a, b, rel, f0)) return -1;
+      c->rep_frames += f1 - f0;
+      if (c->rep_frames % every == 0) {
+        const auto ahead = [&]() -> int {
+          if (f1 < F || Fn <= 0) return 0;
+          ahead_bank = take_bank(c);
+          return build_chunk(c, q, p, ahead_bank, Fn, q.frames + (long)jn * q.stride, c->stream, false, behind, rel);
+        };
+        if (replace_lost(c, q, j0 + f1 - 1, ahead)) return -1;
+      }
+      f0 = f1;
+    }
+  }
   return 0;
 }
 
@@ -594,6 +743,7 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
     }
   }
   if (band) a.escape = band->escape;
+  if (c->rep_on) return track_frames_replacing(c, q, p, a, behind);
   TailRelease rel{p.tail_left, false, 0};
   for (int j0 = 0; j0 < nframes; j0 += p.F) {
     const int F = p.F < nframes - j0 ? p.F : nframes - j0, bi = c->bank_next;
@@ -701,6 +851,9 @@ KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
   if (chunk < 1 || nframes < 0 || n < 0) return fail(c, "track_frames_host: bad nframes/chunk/n");
   if (fb_refused(c, td, false, "track_frames_host")) return -1;
   if (aff_refused(c, td, false, n, "track_frames_host")) return -1;
+  if (c->rep_on && c->aff_on)
+    return fail(c, "track_frames_host: the affine check does not combine with the replacement of lost features "
+                "(klt_hip_set_frames_affine, klt_hip_set_frames_replace)");
   AffCall aff_call(c);
   if (n > 0 && (!x || !y || !val)) return fail(c, "track_frames_host: null feature arrays");
   for (int f = 0; f < nframes; ++f)
@@ -788,6 +941,10 @@ KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
     int *rv = reinterpret_cast<int *>(ry + (size_t)F * n);
     if (ring_ready(k)) return -1;
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_rows[k], 0));  // the rows slot's last D2H is done
+    // a call that replaces lost features blocks on the list inside the chunk:
+    // the next chunk's upload does not depend on it and goes first
+    const bool up_first = c->rep_on && ci + 1 < nchunks;
+    if (up_first && upload(ci + 1)) return -1;
     if (nt > 0 && track_frames_impl(c, pd, td, c->d_ring + (size_t)k * F * fb + skip * fb, pd->ncols, fb, nt, F,
                                     dx, dy, dv, n, rows ? rx : nullptr, rows ? ry : nullptr, rows ? rv : nullptr,
                                     n, nullptr, t0))
@@ -803,7 +960,7 @@ KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
       HIPCHK(c, hipMemcpyAsync(hx + (size_t)2 * F * n, rv, b, hipMemcpyDeviceToHost, c->dstream));
       HIPCHK(c, hipEventRecord(c->ev_rows[k], c->dstream));
     }
-    if (ci + 1 < nchunks && upload(ci + 1)) return -1;  // overlaps chunk ci on the device
+    if (!up_first && ci + 1 < nchunks && upload(ci + 1)) return -1;  // overlaps chunk ci on the device
     if (ci >= 1 && deliver(ci - 1)) return -1;          // and the rows of chunk ci-1
   }
   if (deliver(nchunks - 1)) return -1;
@@ -822,6 +979,8 @@ KLT_API int klt_hip_track_frames_band(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
                                       float *x, float *y, int *val, int n, float own_lo, float own_hi,
                                       int row_lo, int row_hi, int *escape, const unsigned char *next_frames,
                                       int next_nframes) {
+  if (c && c->rep_on)
+    return fail(c, "track_frames_band: not covered while lost features are replaced (klt_hip_set_frames_replace)");
   if (!escape) return fail(c, "track_frames_band: null escape flag");
   BandSpec bs{{own_lo, own_hi}, row_lo, row_hi, escape, next_frames, next_nframes};
   return track_frames_impl(c, pd, td, frames, pitch, stride, nframes, nframes > 0 ? nframes : 1, x, y, val, n,
@@ -858,5 +1017,74 @@ KLT_API int klt_hip_min_eigen_rows(klt_hip_ctx *c, const klt_hip_select_desc *d,
   TimedScope ts(c, T_EIG, c->stream);
   return launched(c, "k_min_eigen", launch_min_eigen(c->stream, L.il ? L.img + kRecGx : L.gx, L.il ? L.img + kRecGy : L.gy,
                                                      L.w, L.il ? 3 : 1, bx, by + j0 * step, step, gx, j1 - j0, hw,
-                                                     hh, dev_map + (long)j0 * gx));
+                                                     hh, dev_map + (long)j0 * gx, &c->eig_kernel));
+}
+
+// the reference's gradient kernels for sigma 1.0 (klt_api.c: taps_make, the C
+// arithmetic of convolve.c:60-114)
+extern "C" void klt_default_grad_taps(klt_hip_taps *gauss, klt_hip_taps *deriv);
+
+KLT_API int klt_hip_min_eigen_plane(klt_hip_ctx *c, const float *dev_img, int ncols, int nrows,
+                                    const klt_hip_select_desc *d, int *dev_map) {
+  if (!c || !dev_img || !d || !dev_map || ncols < 1 || nrows < 1) return fail(c, "min_eigen_plane: bad argument");
+  const int step = d->nSkippedPixels + 1;
+  if (d->window_width != 2 * kRG + 1 || d->window_height != 2 * kRG + 1)
+    return fail(c, "min_eigen_plane: window %dx%d, the kernel covers 7x7 only", d->window_width, d->window_height);
+  if (step < 1 || step > 2) return fail(c, "min_eigen_plane: step %d, the kernel covers 1 and 2", step);
+  if (d->borderx < kRG || d->bordery < kRG) return fail(c, "min_eigen_plane: border smaller than window half size");
+  const int cx = ncols - 2 * d->borderx, cy = nrows - 2 * d->bordery;
+  const int nx = cx > 0 ? (cx + step - 1) / step : 0, ny = cy > 0 ? (cy + step - 1) / step : 0;
+  if ((long)nx * ny == 0) return 0;
+  if (use_device(c)) return -1;
+  klt_hip_taps gg, gd;
+  klt_default_grad_taps(&gg, &gd);
+  if (gg.width != 2 * kRG + 1 || gd.width != 2 * kRG + 1) return fail(c, "min_eigen_plane: default taps are not 7 wide");
+  const RTaps rg = reverse_taps(gg), rd = reverse_taps(gd);
+  GradTaps t;
+  for (int m = 0; m < 2 * kRG + 1; ++m) {
+    t.g[m] = rg.k[m];
+    t.d[m] = rd.k[m];
+  }
+  {
+    TimedScope ts(c, T_EIG, c->stream);
+    if (launched(c, "k_min_eigen7_img", launch_min_eigen_img(c->stream, dev_img, ncols, nrows, t, d->borderx, d->bordery,
+                                                             step, nx, ny, dev_map, &c->eig_kernel)))
+      return -1;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+KLT_API int klt_hip_set_frames_replace(klt_hip_ctx *c, const klt_hip_replace_desc *d) {
+  if (!c) return -1;
+  if (!d) {
+    c->rep_on = 0;
+    return 0;
+  }
+  if (d->every < 1) return fail(c, "set_frames_replace: every %d < 1", d->every);
+  if (d->sel.window_width < 1 || d->sel.window_height < 1)
+    return fail(c, "set_frames_replace: window %dx%d", d->sel.window_width, d->sel.window_height);
+  if (d->sel.borderx < d->sel.window_width / 2 || d->sel.bordery < d->sel.window_height / 2)
+    return fail(c, "set_frames_replace: border smaller than window half size");
+  if (d->sel.nSkippedPixels < 0) return fail(c, "set_frames_replace: bad nSkippedPixels");
+  c->rep = *d;
+  c->rep_on = 1;
+  c->rep_frames = c->rep_runs = c->rep_filled = 0;
+  c->rep_changed.clear();
+  return 0;
+}
+
+KLT_API int klt_hip_get_frames_replace(klt_hip_ctx *c, int *on, long *frames, long *replacements, long *filled) {
+  if (!c) return -1;
+  if (on) *on = c->rep_on;
+  if (frames) *frames = c->rep_frames;
+  if (replacements) *replacements = c->rep_runs;
+  if (filled) *filled = c->rep_filled;
+  return 0;
+}
+
+KLT_API int klt_hip_frames_replace_changed(klt_hip_ctx *c, unsigned char *changed, int n) {
+  if (!c || n < 0 || (n > 0 && !changed)) return fail(c, "frames_replace_changed: bad argument");
+  for (int k = 0; k < n; ++k) changed[k] = (size_t)k < c->rep_changed.size() ? c->rep_changed[k] : 0;
+  return 0;
 }

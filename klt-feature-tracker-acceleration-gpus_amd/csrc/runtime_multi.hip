@@ -46,6 +46,7 @@ KLT_API int klt_hip_track_frames_multi(klt_hip_ctx *c, const klt_hip_pyr_desc *p
                                        int *val, float *tab_x, float *tab_y, int *tab_val, long tab_stride) {
   const char *who = "track_frames_multi";
   if (!c || !pd || !td || !n_seq) return fail(c, "%s: null argument", who);
+  if (c->rep_on) return fail(c, "%s: not covered while lost features are replaced (klt_hip_set_frames_replace)", who);
   if (nseq < 1 || nseq > KLT_HIP_MAX_SEQUENCES)
     return fail(c, "%s: nseq %d is not in 1..%d", who, nseq, KLT_HIP_MAX_SEQUENCES);
   if (nframes < 0 || chunk < 1) return fail(c, "%s: bad nframes/chunk", who);

@@ -616,6 +616,8 @@ KLT_API int klt_hip_track_sequence(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, c
                                    float *x, float *y, int *val, int n, int *cur_slot) {
   if (!c || !pd || !td || !frames || !cur_slot) return fail(c, "track_sequence: null argument");
   if (*cur_slot < 0 || *cur_slot > 2) return fail(c, "track_sequence: cur_slot must be 0, 1 or 2");
+  if (c->rep_on)
+    return fail(c, "track_sequence: not covered while lost features are replaced (klt_hip_set_frames_replace)");
   if (nsteps <= 0) return 0;
   if (fb_refused(c, td, false, "track_sequence") || aff_refused(c, td, false, n, "track_sequence")) return -1;
   AffCall aff_call(c);

@@ -56,6 +56,18 @@ class SelectDesc(C.Structure):
                 ("bordery", C.c_int), ("nSkippedPixels", C.c_int)]
 
 
+class ReplaceDesc(C.Structure):
+    """klt_hip_replace_desc: replacement of lost features inside the batched calls."""
+    _fields_ = [("sel", SelectDesc), ("mindist", C.c_int), ("min_eigenvalue", C.c_int), ("every", C.c_int)]
+
+    @classmethod
+    def from_tc(cls, tc, every: int) -> "ReplaceDesc":
+        """What KLTTrackSequenceReplace passes for this tracking context (a TrackingContextRec)."""
+        sel = SelectDesc(tc.window_width, tc.window_height, max(tc.borderx, tc.window_width // 2),
+                         max(tc.bordery, tc.window_height // 2), tc.nSkippedPixels)
+        return cls(sel, tc.mindist, tc.min_eigenvalue, every)
+
+
 class Timing(C.Structure):
     _fields_ = [("n_pyr_l0", C.c_int), ("n_pyr_l1", C.c_int), ("n_track", C.c_int),
                 ("n_eigen", C.c_int), ("n_generic", C.c_int), ("ms_pyr_l0", C.c_double),
@@ -102,6 +114,11 @@ DEVICE_PROTOS = {
     "klt_hip_affine_get": (C.c_int, [V, IP, C.c_int, FP]),
     "klt_hip_track_affine": (C.c_int, [V, C.c_int, C.c_int, C.POINTER(TrackDesc), C.POINTER(AffineDesc), FP, FP, IP,
                                        FP, IP, C.c_int]),
+    "klt_hip_set_frames_replace": (C.c_int, [V, C.POINTER(ReplaceDesc)]),
+    "klt_hip_get_frames_replace": (C.c_int, [V, IP, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "klt_hip_frames_replace_changed": (C.c_int, [V, V, C.c_int]),
+    "klt_hip_min_eigen_plane": (C.c_int, [V, V, C.c_int, C.c_int, C.POINTER(SelectDesc), V]),
+    "klt_hip_eigen_kernel": (C.c_char_p, [V]),
     "klt_hip_set_track_count": (C.c_int, [V, C.c_int]),
     "klt_hip_get_track_count": (C.c_int, [V, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.c_int]),
     "klt_hip_set_prof": (C.c_int, [V, V]),
