@@ -122,10 +122,60 @@ int klt_hip_device_count(void);
 /* host u8 frame -> device staging buffer `buf` (0 or 1), via pinned memory */
 int klt_hip_upload_frame(klt_hip_ctx *ctx, int buf, const unsigned char *host, int ncols,
                          int nrows);
-/* build pyramid slot `slot` from device u8 frame (row pitch in bytes);
-   frame == NULL -> staging buffer `buf` from klt_hip_upload_frame */
+/* build pyramid slot `slot` from device u8 frame (row pitch in bytes; pixels
+   in the context's frame format, below);
+   frame == NULL -> staging buffer `buf` from klt_hip_upload_frame (gray) */
 int klt_hip_build_pyramid(klt_hip_ctx *ctx, int slot, const klt_hip_pyr_desc *desc,
                           const unsigned char *frame, long pitch, int buf);
+
+/* Pixel format of DEVICE frames: 8-bit gray (default), or interleaved 8-bit
+   RGB / BGR with or without a fourth (alpha) byte, which is ignored.  A colour
+   pixel counts as the gray value
+       gray = (4899*R + 9617*G + 1868*B + 8192) >> 14        (integers)
+   -- the BT.601 luma weights in 14-bit fixed point.  The weights sum to 16384,
+   so white stays 255 and a pixel with R = G = B keeps its value.  This formula
+   is the definition; no equality with any other library's conversion is
+   claimed.  A pyramid, a trackability map or a tracked list made from a colour
+   frame is, byte for byte, what the same call gives on that frame converted
+   by the formula (klt_hip_gray_host, klt_hip_to_gray).
+   The setting covers klt_hip_build_pyramid with frame != NULL,
+   klt_hip_frames_begin, klt_hip_track_frames, klt_hip_track_sequence and
+   klt_hip_track_frames_multi: the conversion happens while the level-0 kernel
+   (or, on the generic pyramid path, its u8 -> f32 pass) loads the pixels, so
+   no gray copy of a frame is written.  pitch, stride and seq_stride stay byte
+   counts, and a call whose pitch < ncols * bytes-per-pixel fails.  Everything
+   downstream reads pyramids and composes unchanged (forward-backward and
+   affine checks, replacement, lazy gradients, every schedule).
+   Host-frame paths stay gray whatever the setting -- klt_hip_upload_frame and
+   pyramids built from its staging buffers, klt_hip_track_frames_host, and the
+   whole klt.h / klt_amd.h surface: colour would triple their bus traffic;
+   convert with klt_hip_gray_host first.  klt_hip_track_frames_band, and with
+   it the sharded drivers (klt_shard.h), fail with -1 and a message before any
+   launch while the format is not gray, leaving the arrays untouched:
+   klt_hip_to_gray is the route for those callers. */
+#define KLT_HIP_FRAME_GRAY8 0
+#define KLT_HIP_FRAME_RGB8 1
+#define KLT_HIP_FRAME_BGR8 2
+#define KLT_HIP_FRAME_RGBA8 3
+#define KLT_HIP_FRAME_BGRA8 4
+/* bytes per pixel of a format: 1, 3, 3, 4, 4; -1 for anything else.  Host only. */
+int klt_hip_frame_bpp(int format);
+/* an unknown format gives -1 with a message and leaves the setting unchanged;
+   klt_hip_ctx_reset restores KLT_HIP_FRAME_GRAY8 */
+int klt_hip_set_frame_format(klt_hip_ctx *ctx, int format);
+int klt_hip_get_frame_format(klt_hip_ctx *ctx);
+/* the formula on the host, no device needed: ncols x nrows pixels of `format`
+   at src (row pitch in bytes) to gray bytes at dst (row pitch dst_pitch);
+   KLT_HIP_FRAME_GRAY8 copies.  -1 for a null pointer, an unknown format,
+   negative sizes, pitch < ncols * bytes-per-pixel or dst_pitch < ncols. */
+int klt_hip_gray_host(int format, const unsigned char *src, long pitch, int ncols, int nrows,
+                      unsigned char *dst, long dst_pitch);
+/* the same on the device, as a plain kernel (k_to_gray) on the context's
+   stream, asynchronous: nframes frames (frame f at dev_src + f*stride, bytes)
+   to gray frames at dev_dst + f*dst_stride.  For callers of the paths that stay
+   gray, and for anyone who wants the gray frame itself. */
+int klt_hip_to_gray(klt_hip_ctx *ctx, int format, const unsigned char *dev_src, long pitch, long stride,
+                    int nframes, int ncols, int nrows, unsigned char *dev_dst, long dst_pitch, long dst_stride);
 /* test hook: 1 forces the generic one-pass-per-launch path even when the
    fused kernels apply (they must agree bit for bit) */
 int klt_hip_set_path(klt_hip_ctx *ctx, int force_generic);
@@ -420,7 +470,9 @@ int klt_hip_track_sequence(klt_hip_ctx *ctx, const klt_hip_pyr_desc *pdesc,
    klt_hip_frames_begin builds the pyramid the first tracked frame starts from;
    klt_hip_track_frames then tracks the device arrays x/y/val (n features)
    through frames[0..nframes-1] (frame f at frames + f*stride, row pitch
-   `pitch`), and leaves the last frame's pyramid as the start of the next call.
+   `pitch`, both in bytes; pixels in the context's frame format,
+   klt_hip_set_frame_format), and leaves the last frame's pyramid as the start
+   of the next call.
    tab_* (device, optional: all three or NULL) receive the list after each
    frame in row f (row stride tab_stride >= n).  Three banks of `chunk`
    pyramids are allocated on first use (and regrown, after draining the
@@ -480,7 +532,8 @@ int klt_hip_frames_end_slot(klt_hip_ctx *ctx, int slot);
    pyramid path (other pyramid parameters, klt_hip_set_path), the generic
    tracker (klt_hip_set_track_impl 1, klt_hip_set_track_patch 0, klt_hip_set_prof);
    nseq < 1 or > KLT_HIP_MAX_SEQUENCES, a negative n_seq[s], nframes < 0,
-   chunk < 1, pitch < ncols, one or two of the three table arrays,
+   chunk < 1, pitch < ncols * bytes per pixel (klt_hip_set_frame_format), one
+   or two of the three table arrays,
    tab_stride < n. */
 #define KLT_HIP_MAX_SEQUENCES 64
 int klt_hip_multi_covers(klt_hip_ctx *ctx, const klt_hip_pyr_desc *pdesc, const klt_hip_track_desc *tdesc);

@@ -110,7 +110,10 @@ int klt_shard_rows(const klt_shard *s, int *lo, int *hi);
    band pyramids are built while this one is exchanged.  x/y/val: n device
    features, updated in place to the merged list.  full: whole frames for a
    redone chunk (required when the chunk escapes).  Returns 0, 1 when the
-   chunk was redone from whole frames, < 0 on error. */
+   chunk was redone from whole frames, < 0 on error.  Frames are 8-bit gray:
+   with a colour klt_hip_set_frame_format on the shard's context this call and
+   klt_shard_eigen fail before any launch or collective (klt_hip_to_gray
+   converts). */
 int klt_shard_track(klt_shard *s, const klt_hip_pyr_desc *pdesc, const klt_hip_track_desc *tdesc,
                     const unsigned char *frames, long pitch, long stride, int nframes,
                     const unsigned char *next_frames, int next_nframes, float *x, float *y, int *val, int n,

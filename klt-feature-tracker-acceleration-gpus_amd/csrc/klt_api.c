@@ -1365,9 +1365,17 @@ EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, i
       for (s = 0; s < nseq; s++) memcpy(stage + ((size_t)j * nseq + s) * fb, frames[s][j0 + j], fb);
     /* synchronous: the previous group's device work is done, the staging is free again on return */
     dev_check(tc, klt_hip_memcpy(dev, dfr, stage, (size_t)(nf + 1) * nseq * fb, MEMCPY_H2D), "sequences: upload");
-    dev_check(tc, klt_hip_track_frames_multi(dev, &D, &td, dfr, ncols, (long)(nseq * fb), (long)fb, nseq, nf, nf,
-                                             counts, dx, dy, dv, dtx, dty, dtv, n),
-              "sequences: tracking");
+    {
+      /* the klt.h surface takes gray host frames, whatever format the device
+         context (klt_amd_device_context) has been given for device frames */
+      const int fmt = klt_hip_get_frame_format(dev);
+      int rc;
+      klt_hip_set_frame_format(dev, KLT_HIP_FRAME_GRAY8);
+      rc = klt_hip_track_frames_multi(dev, &D, &td, dfr, ncols, (long)(nseq * fb), (long)fb, nseq, nf, nf, counts, dx,
+                                      dy, dv, dtx, dty, dtv, n);
+      klt_hip_set_frame_format(dev, fmt);
+      dev_check(tc, rc, "sequences: tracking");
+    }
     if (any_ft && n > 0) {
       int c0 = 0;
       dev_check(tc, klt_hip_memcpy(dev, tx, dtx, sizeof(float) * (size_t)nf * n, MEMCPY_D2H), "sequences: rows");

@@ -1,8 +1,9 @@
 // klt_dev.h -- internal interface between the gfx950 kernel files and the host
 // runtime of libklt_amd.so (not installed, not part of the C ABI).
 //
-//   pyramid.hip   k_pyr_l0 / k_pyr_l1 (fused default-parameter pyramid),
-//                 the generic one-pass kernels, k_min_eigen, k_synth
+//   pyramid.hip   k_pyr_l0 / k_pyr_l1 (fused default-parameter pyramid; k_pyr_l0_px
+//                 from colour pixels), the generic one-pass kernels, k_to_gray,
+//                 k_min_eigen, k_synth
 //   track.hip     k_track_frames_g (the Newton loop for any window, one wave per
 //                 feature; the _g is only a name), k_band_order
 //   track7.hip    k_track7 (the Newton loop of the default configuration)
@@ -91,6 +92,26 @@ constexpr int kRecGx = 0, kRecGy = 1, kRecImg = 2, kRec = 3;
 // records, or -- level 0 of a bank whose tracker computes its own windows'
 // gradients from the image (klt_hip_set_lazy_grad) -- the img plane alone
 constexpr int kLayoutPlanes = 0, kLayoutRec = 1, kLayoutImg = 2;
+
+// Colour device frames (klt_hip_set_frame_format): interleaved 8-bit channels,
+// 3 or 4 bytes a pixel.  gray = (4899 R + 9617 G + 1868 B + 8192) >> 14, the
+// BT.601 weights in 14-bit fixed point (they sum to 1 << 14); alpha is ignored.
+// One definition for the device kernels and klt_hip_gray_host.
+constexpr uint32_t kGrayR = 4899, kGrayG = 9617, kGrayB = 1868, kGrayHalf = 8192;
+constexpr int kGrayShift = 14;
+static_assert(kGrayR + kGrayG + kGrayB == (1u << kGrayShift), "white stays 255");
+// bytes per pixel of a KLT_HIP_FRAME_* format; -1: not a format
+constexpr int frame_bpp(int fmt) {
+  return fmt == KLT_HIP_FRAME_GRAY8                                 ? 1
+         : (fmt == KLT_HIP_FRAME_RGB8 || fmt == KLT_HIP_FRAME_BGR8)   ? 3
+         : (fmt == KLT_HIP_FRAME_RGBA8 || fmt == KLT_HIP_FRAME_BGRA8) ? 4
+                                                                      : -1;
+}
+// the weights of a pixel's bytes 0 and 2 (byte 1 is green in every format)
+constexpr bool frame_bgr(int fmt) { return fmt == KLT_HIP_FRAME_BGR8 || fmt == KLT_HIP_FRAME_BGRA8; }
+__host__ __device__ __forceinline__ uint32_t gray_of(uint32_t c0, uint32_t c1, uint32_t c2, bool bgr) {
+  return ((bgr ? kGrayB : kGrayR) * c0 + kGrayG * c1 + (bgr ? kGrayR : kGrayB) * c2 + kGrayHalf) >> kGrayShift;
+}
 
 // tile geometry the runtime needs for grids and band bookkeeping
 namespace geom {
@@ -244,7 +265,11 @@ constexpr int kAffChunk = KLT_AFF_CH;
 // il: kLayoutPlanes, kLayoutRec, or kLayoutImg (img as a plane, no gradients)
 hipError_t launch_pyr_l0(hipStream_t st, const uint8_t *src, int pitch, long stride, int W, int H, const DefTaps &T,
                          int vec_u8, int vec_out, float *img, float *gx, float *gy, float *hs, int W1, int do_hs,
-                         long fs0, long fsh, int F, int ty0, int ty1, int py0 = 0, int py1 = 1 << 30, int il = 0);
+                         long fs0, long fsh, int F, int ty0, int ty1, int py0 = 0, int py1 = 1 << 30, int il = 0,
+                         int fmt = KLT_HIP_FRAME_GRAY8);
+// fmt: the source pixels' format (KLT_HIP_FRAME_*); pitch and stride are bytes.
+// A colour format runs the k_pyr_l0_px instances, whose phase A stages the
+// gray bytes of gray_of(); everything after phase A is k_pyr_l0's
 // k_pyr_l1 over F frames, level-1 tile rows [ty0, ty1)
 // il != 0 (both): the planes interleaved per pixel, {gx, gy, img} at img + 3*(y*w + x); gx/gy unused
 // thin: 8-row tiles (ty0/ty1 in those), for a single frame; else geom::L1_TH rows
@@ -254,6 +279,12 @@ hipError_t launch_pyr_l1(hipStream_t st, const float *hs, int W1, int H, int H1,
 constexpr int kL1ThinRows = 8;  // launch_pyr_l1's thin tiles
 // generic one-pass kernels (any sigma / levels / subsampling)
 hipError_t launch_u8_to_f32(hipStream_t st, const uint8_t *src, long pitch, int W, int H, float *out);
+// the same from colour pixels: float(gray_of(pixel)) (fmt: a colour KLT_HIP_FRAME_* format)
+hipError_t launch_px_to_f32(hipStream_t st, const uint8_t *src, long pitch, int W, int H, int fmt, float *out);
+// n frames of fmt pixels (src + f*stride, row pitch in bytes) to gray bytes
+// (dst + f*dstride, row pitch dpitch); gray frames are copied
+hipError_t launch_to_gray(hipStream_t st, int fmt, const uint8_t *src, long pitch, long stride, int n, int W, int H,
+                          uint8_t *dst, long dpitch, long dstride);
 hipError_t launch_rows(hipStream_t st, const float *in, int W, int H, const RTaps &t, float *out);
 hipError_t launch_cols(hipStream_t st, const float *in, int W, int H, const RTaps &t, float *out);
 hipError_t launch_subsample(hipStream_t st, const float *in, int W, int ss, float *out, int W1, int H1);

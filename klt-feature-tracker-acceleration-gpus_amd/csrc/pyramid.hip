@@ -3,8 +3,12 @@
 //                         (_KLTToFloatImage + _KLTComputeSmoothedImage +
 //                          _KLTComputePyramid + _KLTComputeGradients,
 //                          convolve.c:37-53,273-314; pyramid.c:87-131)
+//   k_pyr_l0_px           k_pyr_l0 from RGB/BGR(A) pixels: phase A converts
+//                         as it stages (klt_hip_set_frame_format)
 //   k_u8_to_f32 / k_rows / k_cols / k_subsample   the generic path (any sigma,
-//                         levels, subsampling), one 1-D pass per launch
+//                         levels, subsampling), one 1-D pass per launch;
+//   k_px_to_f32           its first pass from colour pixels
+//   k_to_gray             colour frames to gray frames (klt_hip_to_gray)
 //   k_min_eigen           the trackability map (selectGoodFeatures.c:375-424);
 //   k_min_eigen7_img      the same from a level-0 img plane alone
 //   k_synth               synthetic frames (include/klt_synth.h)
@@ -177,13 +181,121 @@ __device__ unsigned long long *g_pyr_prof;
 #define PYR_END()
 #endif
 
+// Colour source pixels (KLT_HIP_FRAME_*, klt_dev.h): the format is a
+// compile-time parameter of the loads alone.  Four pixels make one staged
+// dword of gray bytes -- from three source dwords at 3 bytes a pixel, from
+// four (one 16-byte load) at 4.
+template <int FMT>
+struct Px {
+  static constexpr int BPP = frame_bpp(FMT);
+  static constexpr bool BGR = frame_bgr(FMT);
+  static_assert(BPP == 1 || BPP == 3 || BPP == 4, "a KLT_HIP_FRAME_* format");
+};
+// 16 bytes at a 4-byte boundary: 3 bytes a pixel puts a chunk's first byte at
+// a multiple of 12 from the row's start, and base and pitch are only 4-byte
+// aligned for either pixel size.  gfx950 takes a dwordx4 load at any dword.
+typedef uint32_t u4a __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ u4a ld16a(const uint8_t *p) { return *reinterpret_cast<const u4a *>(p); }
+template <int FMT>
+__device__ __forceinline__ uint32_t gray4_of3(uint32_t d0, uint32_t d1, uint32_t d2) {
+  constexpr bool S = Px<FMT>::BGR;
+  return gray_of(d0 & 0xFF, (d0 >> 8) & 0xFF, (d0 >> 16) & 0xFF, S) |
+         (gray_of(d0 >> 24, d1 & 0xFF, (d1 >> 8) & 0xFF, S) << 8) |
+         (gray_of((d1 >> 16) & 0xFF, d1 >> 24, d2 & 0xFF, S) << 16) |
+         (gray_of((d2 >> 8) & 0xFF, (d2 >> 16) & 0xFF, d2 >> 24, S) << 24);
+}
+template <int FMT>
+__device__ __forceinline__ uint32_t gray4_of4(u4a d) {
+  constexpr bool S = Px<FMT>::BGR;
+  return gray_of(d.x & 0xFF, (d.x >> 8) & 0xFF, (d.x >> 16) & 0xFF, S) |
+         (gray_of(d.y & 0xFF, (d.y >> 8) & 0xFF, (d.y >> 16) & 0xFF, S) << 8) |
+         (gray_of(d.z & 0xFF, (d.z >> 8) & 0xFF, (d.z >> 16) & 0xFF, S) << 16) |
+         (gray_of(d.w & 0xFF, (d.w >> 8) & 0xFF, (d.w >> 16) & 0xFF, S) << 24);
+}
+// the staged dword of pixels x .. x+3 of a row (x % 4 == 0; 4-byte aligned row)
+template <int FMT>
+__device__ __forceinline__ uint32_t gray4_at(const uint8_t *row, int x) {
+  const uint8_t *p = row + Px<FMT>::BPP * x;
+  if constexpr (Px<FMT>::BPP == 4) {
+    return gray4_of4<FMT>(ld16a(p));
+  } else {
+    const uint32_t *d = reinterpret_cast<const uint32_t *>(p);
+    return gray4_of3<FMT>(d[0], d[1], d[2]);
+  }
+}
+// the 16 gray bytes of pixels x .. x+15: every load issued before the first is used
+template <int FMT>
+__device__ __forceinline__ uint4 gray16_at(const uint8_t *row, int x) {
+  const uint8_t *p = row + Px<FMT>::BPP * x;
+  if constexpr (Px<FMT>::BPP == 4) {
+    const u4a a = ld16a(p), b = ld16a(p + 16), c = ld16a(p + 32), d = ld16a(p + 48);
+    return uint4{gray4_of4<FMT>(a), gray4_of4<FMT>(b), gray4_of4<FMT>(c), gray4_of4<FMT>(d)};
+  } else {
+    const u4a a = ld16a(p), b = ld16a(p + 16), c = ld16a(p + 32);
+    return uint4{gray4_of3<FMT>(a.x, a.y, a.z), gray4_of3<FMT>(a.w, b.x, b.y), gray4_of3<FMT>(b.z, b.w, c.x),
+                 gray4_of3<FMT>(c.y, c.z, c.w)};
+  }
+}
+
+// Phase A of pyr_l0_tile from colour pixels: the same three staging paths,
+// rows, clamps and LDS places as the gray ones below, each staged byte the
+// gray value of its pixel.  vec_u8 here: base, pitch and frame stride 4-byte
+// aligned and W % 4 == 0, so every 4-pixel group starts on a dword and lies
+// wholly inside or outside the frame.
+template <bool INT, class G, int FMT>
+__device__ __forceinline__ void pyr_l0_stage_px(float *__restrict__ u, const uint8_t *__restrict__ src, int spitch,
+                                                int W, int H, int vec_u8, int C0, int R0, int tid) {
+  constexpr int RS = G::RS, HR = G::HR, NT = G::NT, UQ = G::UQ, UH = G::UH, PUB = G::PUB, NQ = G::NQ, NR = G::NR;
+  constexpr int BPP = Px<FMT>::BPP;
+  if constexpr (INT) {
+    const int i = min(tid, NR * NQ - 1);
+    const int r = i / NQ, q = i - r * NQ;
+    const uint4 c = gray16_at<FMT>(src + (unsigned)((R0 - HR - RS + r) * spitch), C0 - 12 + 16 * q);
+    *reinterpret_cast<uint4 *>(reinterpret_cast<uint32_t *>(u) + r * PUB + 4 * q) = c;
+  } else if (vec_u8) {
+    const int i = min(tid, NR * NQ - 1);
+    const int r = i / NQ, q = i - r * NQ;
+    const uint8_t *row = src + (unsigned)(clampi(R0 - HR - RS + r, 0, H - 1) * spitch);
+    const int x = C0 - 12 + 16 * q;
+    uint4 c;
+    if (x >= 0 && x + 16 <= W) {
+      c = gray16_at<FMT>(row, x);
+    } else {
+      c.x = gray4_at<FMT>(row, clampi(x, 0, W - 4));
+      c.y = gray4_at<FMT>(row, clampi(x + 4, 0, W - 4));
+      c.z = gray4_at<FMT>(row, clampi(x + 8, 0, W - 4));
+      c.w = gray4_at<FMT>(row, clampi(x + 12, 0, W - 4));
+    }
+    *reinterpret_cast<uint4 *>(reinterpret_cast<uint32_t *>(u) + r * PUB + 4 * q) = c;
+  } else {
+    constexpr int NA = UH * UQ, PER = (NA + NT - 1) / NT;
+    static_assert(PER * NT <= G::REG_A, "phase A spill-over stays inside region A");
+    // a dword of four pixels per item and pass, written as soon as it is made:
+    // twelve byte loads an item, no reason to hold every pass's in registers
+    for (int k = 0; k < PER; ++k) {
+      const int i = min(tid + k * NT, NA - 1);
+      const int r = i / UQ, q = i - r * UQ;
+      const int x = C0 - 12 + 4 * q;
+      const uint8_t *row = src + (unsigned)(clampi(R0 - HR - RS + r, 0, H - 1) * spitch);
+      uint32_t w = 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint8_t *p = row + BPP * clampi(x + e, 0, W - 1);
+        w |= gray_of(p[0], p[1], p[2], Px<FMT>::BGR) << (8 * e);
+      }
+      reinterpret_cast<uint32_t *>(u)[r * PUB + q] = w;
+    }
+  }
+}
+
 // Edge tiles (INT false) clamp their loads and apply the zero-border rules per
 // element; interior tiles (~90 % at 1080p, 94 % at 4K) need neither.
 // IL: the level's planes interleaved per pixel, {gx, gy, img} (12 bytes, klt_dev.h)
 // at img0 + 3*(y*W + x) -- written in E, where img0 is still in LDS; gx0/gy0 unused
 // IMG (with IL false): the image-only instance -- phases A-C, img0 as a plane
 // (D1) and the sigma-3.6 rows pass (D3); no gradient passes, no halo rows
-template <bool INT, bool IL, int TH_, bool IMG = false>
+// FMT: the source pixels (KLT_HIP_FRAME_*); colour formats differ in phase A alone
+template <bool INT, bool IL, int TH_, bool IMG = false, int FMT = KLT_HIP_FRAME_GRAY8>
 __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8_t *__restrict__ src, int spitch,
                                             int W, int H, const DefTaps &T, int vec_u8,
                                             float *__restrict__ img0, float *__restrict__ gx0,
@@ -203,7 +315,9 @@ __device__ __forceinline__ void pyr_l0_tile(float *__restrict__ lds, const uint8
   float *txy = lds + REG_A;  // IL: [IH][PXY], {tx, ty} per pixel (after t1 is dead)
 
   // A. u8 tile + halo -> LDS; every load issued before the first is used
-  if constexpr (INT) {
+  if constexpr (FMT != KLT_HIP_FRAME_GRAY8) {
+    pyr_l0_stage_px<INT, G, FMT>(u, src, spitch, W, H, vec_u8, C0, R0, tid);
+  } else if constexpr (INT) {
     // interior tile: one 16-byte load per thread, 6 per staged row at
     // C0-12+16q (dword-aligned: vec_u8 guarantees a 4-byte pitch and base),
     // rows R0-5 .. R0+36 -- the 42 rows any stored output reads.  Rows 42-43
@@ -607,6 +721,43 @@ __global__ __launch_bounds__(L0G<TH_>::NT) void k_pyr_l0(const uint8_t *__restri
                                 threadIdx.x, planes, cols_in, rows_in);
 }
 
+// k_pyr_l0 from colour pixels (FMT: KLT_HIP_FRAME_RGB8 .. BGRA8), kernels of
+// their own so that the gray instances keep their names and their code: the
+// same arguments (spitch and fs_src in bytes, as there), the same tiles and
+// LDS; phase A converts as it stages (pyr_l0_stage_px), phases B-E are shared.
+template <bool IL, int TH_, bool IMG, int FMT>
+__global__ __launch_bounds__(L0G<TH_>::NT) void k_pyr_l0_px(const uint8_t *__restrict__ src, int spitch, int W, int H,
+                                                      DefTaps T, int vec_u8, float *__restrict__ img0,
+                                                      float *__restrict__ gx0, float *__restrict__ gy0,
+                                                      float *__restrict__ hs, int hsW, int do_hs, int vec_out,
+                                                      long fs_src, long fs0, long fs_hs, int ty0, int tiles_x,
+                                                      int tiles_y, int py0, int py1) {
+  static_assert(FMT != KLT_HIP_FRAME_GRAY8, "gray frames take k_pyr_l0");
+  using G = L0G<TH_, IMG ? 0 : kRG>;
+  __shared__ __attribute__((aligned(16))) float lds[G::LDS];
+  int bx, by;
+  if (!xcd_tile(tiles_x, tiles_y, bx, by)) return;  // whole workgroup: no barrier is skipped
+#ifdef KLT_PYR_PROF
+  const int tid = threadIdx.x;
+  PYR_STAMP(0)
+#endif
+  const int C0 = bx * G::TW, R0 = (by + ty0) * G::TH;
+  src += blockIdx.z * fs_src;
+  img0 += blockIdx.z * fs0;
+  gx0 += blockIdx.z * fs0;
+  gy0 += blockIdx.z * fs0;
+  hs += blockIdx.z * fs_hs;
+  const bool cols_in = C0 >= 12 && C0 + 84 <= W, rows_in = R0 >= 5 && R0 + G::TH + 7 <= H;
+  const bool interior = vec_u8 && vec_out && (hsW * G::SS == W) && (hsW % 2 == 0) && cols_in && rows_in;
+  const bool planes = by + ty0 >= py0 && by + ty0 < py1;
+  if (interior)
+    pyr_l0_tile<true, IL, TH_, IMG, FMT>(lds, src, spitch, W, H, T, vec_u8, img0, gx0, gy0, hs, hsW, do_hs, vec_out, C0,
+                                         R0, threadIdx.x, planes, true, true);
+  else
+    pyr_l0_tile<false, IL, TH_, IMG, FMT>(lds, src, spitch, W, H, T, vec_u8, img0, gx0, gy0, hs, hsW, do_hs, vec_out, C0,
+                                          R0, threadIdx.x, planes, cols_in, rows_in);
+}
+
 // ---------------------------------------------------------------------------
 // k_pyr_l1: img1 = cols_p(hs) sampled at rows 4Y+2 (rest of pyramid.c:114-124)
 // and its gradients.  One 256-thread workgroup per 32 x TH tile of level 1:
@@ -807,6 +958,43 @@ __global__ __launch_bounds__(kBlock) void k_u8_to_f32(const uint8_t *__restrict_
   if (i >= (long)W * H) return;
   const int y = (int)(i / W), x = (int)(i - (long)y * W);
   out[i] = (float)src[(long)y * spitch + x];
+}
+
+// the same from colour pixels (bpp bytes each, gray_of's byte order in bgr)
+__global__ __launch_bounds__(kBlock) void k_px_to_f32(const uint8_t *__restrict__ src, long spitch, int W, int H,
+                                                      int bpp, int bgr, float *__restrict__ out) {
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= (long)W * H) return;
+  const int y = (int)(i / W), x = (int)(i - (long)y * W);
+  const uint8_t *p = src + (long)y * spitch + (long)bpp * x;
+  out[i] = (float)gray_of(p[0], p[1], p[2], bgr != 0);
+}
+
+// k_to_gray: frames of FMT pixels to gray bytes (klt_hip_to_gray), a thread
+// per four pixels of a row, blockIdx.y the frame.  vec (both sides' base,
+// pitch and frame stride 4-byte aligned, W % 4 == 0): dword loads and one
+// dword store, consecutive lanes at consecutive groups; else byte by byte.
+// A gray source is copied.
+template <int FMT>
+__global__ __launch_bounds__(kBlock) void k_to_gray(const uint8_t *__restrict__ src, long spitch, long sstride, int W,
+                                                    int H, int vec, uint8_t *__restrict__ dst, long dpitch,
+                                                    long dstride) {
+  const int W4 = (W + 3) / 4;
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= (long)W4 * H) return;
+  const int y = (int)(i / W4), x = 4 * (int)(i - (long)y * W4);
+  const uint8_t *row = src + blockIdx.y * sstride + (long)y * spitch;
+  uint8_t *o = dst + blockIdx.y * dstride + (long)y * dpitch + x;
+  if (vec) {
+    if constexpr (FMT == KLT_HIP_FRAME_GRAY8) *reinterpret_cast<uint32_t *>(o) = *reinterpret_cast<const uint32_t *>(row + x);
+    else *reinterpret_cast<uint32_t *>(o) = gray4_at<FMT>(row, x);
+    return;
+  }
+  for (int e = 0; e < 4 && x + e < W; ++e) {
+    const uint8_t *p = row + Px<FMT>::BPP * (x + e);
+    if constexpr (FMT == KLT_HIP_FRAME_GRAY8) o[e] = p[0];
+    else o[e] = (uint8_t)gray_of(p[0], p[1], p[2], Px<FMT>::BGR);
+  }
 }
 
 __global__ __launch_bounds__(kBlock) void k_rows(const float *__restrict__ in, int W, int H, RTaps t,
@@ -1146,11 +1334,62 @@ bool l0_wide() {
   return on;
 }
 
+namespace {
+// launch_pyr_l0 for a colour format: the same choice of tiles and instance
+template <int FMT>
+hipError_t launch_pyr_l0_px(hipStream_t st, const uint8_t *src, int pitch, long stride, int W, int H, const DefTaps &T,
+                            int vec_u8, int vec_out, float *img, float *gx, float *gy, float *hs, int W1, int do_hs,
+                            long fs0, long fsh, int F, int ty0, int ty1, int py0, int py1, int il) {
+  const int tx = (W + l0::TW - 1) / l0::TW;
+  const int nty = (H + l0::G32::TH - 1) / l0::G32::TH;
+  if (l0_wide() && H >= kL0WideMinRows && ty0 == 0 && ty1 == nty && py0 == 0 && py1 >= nty) {
+    using G = L0G<64>;
+    const int ty = (H + G::TH - 1) / G::TH;
+    const dim3 grid(xcd_grid(tx * ty), 1, F);
+    if (il == kLayoutImg)
+      hipLaunchKernelGGL((k_pyr_l0_px<false, 64, true, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8, img,
+                         gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
+    else if (il)
+      hipLaunchKernelGGL((k_pyr_l0_px<true, 64, false, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8, img,
+                         gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
+    else
+      hipLaunchKernelGGL((k_pyr_l0_px<false, 64, false, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8,
+                         img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
+    return hipGetLastError();
+  }
+  using G = l0::G32;
+  const dim3 grid(xcd_grid(tx * (ty1 - ty0)), 1, F);
+  if (il == kLayoutImg)
+    hipLaunchKernelGGL((k_pyr_l0_px<false, 32, true, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8, img,
+                       gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0, py0, py1);
+  else if (il)
+    hipLaunchKernelGGL((k_pyr_l0_px<true, 32, false, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8, img,
+                       gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0, py0, py1);
+  else
+    hipLaunchKernelGGL((k_pyr_l0_px<false, 32, false, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8, img,
+                       gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0, py0, py1);
+  return hipGetLastError();
+}
+}  // namespace
+
 hipError_t launch_pyr_l0(hipStream_t st, const uint8_t *src, int pitch, long stride, int W, int H, const DefTaps &T,
                          int vec_u8, int vec_out, float *img, float *gx, float *gy, float *hs, int W1, int do_hs,
-                         long fs0, long fsh, int F, int ty0, int ty1, int py0, int py1, int il) {
+                         long fs0, long fsh, int F, int ty0, int ty1, int py0, int py1, int il, int fmt) {
   const int tx = (W + l0::TW - 1) / l0::TW;
   if (F <= 0 || ty1 <= ty0) return hipSuccess;
+  switch (fmt) {
+    case KLT_HIP_FRAME_GRAY8: break;
+#define KLT_L0_PX(f)                                                                                               \
+  case f:                                                                                                          \
+    return launch_pyr_l0_px<f>(st, src, pitch, stride, W, H, T, vec_u8, vec_out, img, gx, gy, hs, W1, do_hs, fs0, \
+                               fsh, F, ty0, ty1, py0, py1, il);
+      KLT_L0_PX(KLT_HIP_FRAME_RGB8)
+      KLT_L0_PX(KLT_HIP_FRAME_BGR8)
+      KLT_L0_PX(KLT_HIP_FRAME_RGBA8)
+      KLT_L0_PX(KLT_HIP_FRAME_BGRA8)
+#undef KLT_L0_PX
+    default: return hipErrorInvalidValue;  // a missing instance is an error, never the gray kernel
+  }
 #ifdef KLT_EXP_NOHS  // timing experiment only: level 0 without the sigma-3.6 rows pass
   do_hs = 0;
 #endif
@@ -1217,6 +1456,45 @@ hipError_t launch_u8_to_f32(hipStream_t st, const uint8_t *src, long pitch, int 
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_u8_to_f32, dim3(blocks_for(n)), dim3(kBlock), 0, st, src, pitch, W, H, out);
   return hipGetLastError();
+}
+
+hipError_t launch_px_to_f32(hipStream_t st, const uint8_t *src, long pitch, int W, int H, int fmt, float *out) {
+  const long n = (long)W * H;
+  if (frame_bpp(fmt) < 3) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_px_to_f32, dim3(blocks_for(n)), dim3(kBlock), 0, st, src, pitch, W, H, frame_bpp(fmt),
+                     frame_bgr(fmt) ? 1 : 0, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_to_gray(hipStream_t st, int fmt, const uint8_t *src, long pitch, long stride, int n, int W, int H,
+                          uint8_t *dst, long dpitch, long dstride) {
+  if (frame_bpp(fmt) < 0) return hipErrorInvalidValue;
+  const long items = (long)((W + 3) / 4) * H;
+  if (items == 0) return hipSuccess;
+  const auto al4 = [](const void *p, long a, long b) { return (((uintptr_t)p | (uintptr_t)a | (uintptr_t)b) & 3) == 0; };
+  const int vec = (W % 4 == 0 && al4(src, pitch, stride) && al4(dst, dpitch, dstride)) ? 1 : 0;
+  for (int f0 = 0; f0 < n; f0 += 65535) {
+    const int cnt = (n - f0) < 65535 ? (n - f0) : 65535;
+    const dim3 grid(blocks_for(items), cnt);
+    const uint8_t *s = src + (long)f0 * stride;
+    uint8_t *d = dst + (long)f0 * dstride;
+    switch (fmt) {
+#define KLT_TO_GRAY(f)                                                                                           \
+  case f:                                                                                                        \
+    hipLaunchKernelGGL(k_to_gray<f>, grid, dim3(kBlock), 0, st, s, pitch, stride, W, H, vec, d, dpitch, dstride); \
+    break;
+      KLT_TO_GRAY(KLT_HIP_FRAME_GRAY8)
+      KLT_TO_GRAY(KLT_HIP_FRAME_RGB8)
+      KLT_TO_GRAY(KLT_HIP_FRAME_BGR8)
+      KLT_TO_GRAY(KLT_HIP_FRAME_RGBA8)
+      KLT_TO_GRAY(KLT_HIP_FRAME_BGRA8)
+#undef KLT_TO_GRAY
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t launch_rows(hipStream_t st, const float *in, int W, int H, const RTaps &t, float *out) {

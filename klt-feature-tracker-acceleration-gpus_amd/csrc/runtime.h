@@ -152,6 +152,11 @@ struct __attribute__((visibility("default"))) klt_hip_ctx {  // its constructor 
   size_t astate_cap = 0, aidx_cap = 0;
   std::string err;
   int force_generic = 0;
+  // klt_hip_set_frame_format: the pixels of device frames (KLT_HIP_FRAME_*).
+  // Read where a caller's device frame enters a pyramid build (build_pyramid_on
+  // with a frame, build_fused_bank); the host-frame paths hold it at gray
+  // for their own device copies (GrayFrames)
+  int frame_format = KLT_HIP_FRAME_GRAY8;
   int track_order = 0;  // 0: band-sorted, XCD-major processing order; 1: input order
   int track_patch = 1;  // one-feature waves gather through a lane patch when the window fits
   int track_merge = 1;   // defer finest-level residues into the next frame's first pass (ResCarry)
@@ -393,6 +398,26 @@ struct AffCall {
     if (c) --c->aff_depth;
   }
 };
+
+// a host-frame entry point: its device copies of the caller's frames are gray
+// whatever klt_hip_set_frame_format says
+struct GrayFrames {
+  klt_hip_ctx *c;
+  int saved;
+  explicit GrayFrames(klt_hip_ctx *ctx) : c(ctx), saved(ctx ? ctx->frame_format : 0) {
+    if (c) c->frame_format = KLT_HIP_FRAME_GRAY8;
+  }
+  ~GrayFrames() {
+    if (c) c->frame_format = saved;
+  }
+};
+
+// the fused level-0 kernels' vectorised loads: base, row pitch and frame stride
+// (bytes) 4-byte aligned, and whole 4-pixel groups (any pixel size: 4 pixels
+// are 4, 12 or 16 bytes)
+inline int vec_u8_ok(const uint8_t *src, long pitch, long stride, int W) {
+  return (W % 4 == 0 && W >= 16 && pitch % 4 == 0 && stride % 4 == 0 && ((uintptr_t)src & 3) == 0) ? 1 : 0;
+}
 
 // track_frames_launch: ordered: the caller ran order_features into b already;
 // fb_row: the forward-backward / affine table row of this launch's first

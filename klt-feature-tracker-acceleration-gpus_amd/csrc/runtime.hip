@@ -303,6 +303,7 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->chunk_used = 0;
   c->stream = c->own;
   c->force_generic = 0;
+  c->frame_format = KLT_HIP_FRAME_GRAY8;
   c->track_order = 0;
   c->track_patch = 1;
   c->track_merge = 1;

@@ -285,7 +285,12 @@ int frames_check(klt_hip_ctx *c, const FramesCall &q, int chunk) {
   const int ntab = (q.tab_x != nullptr) + (q.tab_y != nullptr) + (q.tab_val != nullptr);
   if (ntab != 0 && ntab != 3) return fail(c, "track_frames: give all three table arrays or none");
   if (ntab && q.tab_stride < n) return fail(c, "track_frames: table stride %ld < n %d", q.tab_stride, n);
-  if (q.pitch < pd->ncols) return fail(c, "track_frames: pitch %ld < ncols %d", q.pitch, pd->ncols);
+  if (q.band && c->frame_format != KLT_HIP_FRAME_GRAY8)
+    return fail(c, "track_frames_band: colour frames are not covered (klt_hip_set_frame_format %d); convert with "
+                "klt_hip_to_gray", c->frame_format);
+  if (q.pitch < (long)pd->ncols * frame_bpp(c->frame_format))
+    return fail(c, "track_frames: pitch %ld < ncols %d * %d bytes per pixel", q.pitch, pd->ncols,
+                frame_bpp(c->frame_format));
   if (check_window(c, q.td)) return -1;
   if (c->rep_on && c->aff_on)
     return fail(c, "track_frames: the affine check does not combine with the replacement of lost features "
@@ -849,6 +854,7 @@ KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
                                       float *x, float *y, int *val, int n, klt_hip_rows_fn rows, void *user) {
   if (!c || !pd || !td || (nframes > 0 && !frames)) return fail(c, "track_frames_host: null argument");
   if (chunk < 1 || nframes < 0 || n < 0) return fail(c, "track_frames_host: bad nframes/chunk/n");
+  const GrayFrames gray_ring(c);  // host frames are gray: so is the upload ring the calls below read
   if (fb_refused(c, td, false, "track_frames_host")) return -1;
   if (aff_refused(c, td, false, n, "track_frames_host")) return -1;
   if (c->rep_on && c->aff_on)

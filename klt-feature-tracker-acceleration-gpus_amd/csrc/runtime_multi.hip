@@ -67,7 +67,8 @@ KLT_API int klt_hip_track_frames_multi(klt_hip_ctx *c, const klt_hip_pyr_desc *p
   const int ntab = (tab_x != nullptr) + (tab_y != nullptr) + (tab_val != nullptr);
   if (ntab != 0 && ntab != 3) return fail(c, "%s: give all three table arrays or none", who);
   if (ntab && tab_stride < n) return fail(c, "%s: table stride %ld < n %d", who, tab_stride, n);
-  if (pitch < pd->ncols) return fail(c, "%s: pitch %ld < ncols %d", who, pitch, pd->ncols);
+  if (pitch < (long)pd->ncols * frame_bpp(c->frame_format))
+    return fail(c, "%s: pitch %ld < ncols %d * %d bytes per pixel", who, pitch, pd->ncols, frame_bpp(c->frame_format));
   if (multi_refused(c, pd, td)) return -1;
   if (nframes == 0) return 0;
   if (use_device(c)) return -1;

@@ -35,8 +35,14 @@ int ensure_slot(klt_hip_ctx *c, int s, const klt_hip_pyr_desc *d) {
 }
 
 namespace {
+// the level-0 input as floats: the generic path's first pass (fmt: the source pixels)
+hipError_t to_f32(hipStream_t st, const uint8_t *src, long pitch, int W, int H, int fmt, float *out) {
+  return fmt == KLT_HIP_FRAME_GRAY8 ? launch_u8_to_f32(st, src, pitch, W, H, out)
+                                    : launch_px_to_f32(st, src, pitch, W, H, fmt, out);
+}
+
 int build_generic(klt_hip_ctx *c, int s, const klt_hip_pyr_desc *d, const uint8_t *src, long pitch,
-                  hipStream_t st) {
+                  hipStream_t st, int fmt) {
   Slot &S = c->slot[s];
   for (int l = 0; l < d->nlevels; ++l) S.lv[l].il = 0;  // planes
   const long n0 = (long)d->ncols * d->nrows;
@@ -49,12 +55,12 @@ int build_generic(klt_hip_ctx *c, int s, const klt_hip_pyr_desc *d, const uint8_
   float *t0 = c->d_tmp[0], *t1 = c->d_tmp[1];
   if (n0 > 0) {
     if (d->smooth_input) {
-      if (launched(c, "k_u8_to_f32", launch_u8_to_f32(st, src, pitch, d->ncols, d->nrows, t1)) ||
+      if (launched(c, "k_u8_to_f32", to_f32(st, src, pitch, d->ncols, d->nrows, fmt, t1)) ||
           launched(c, "k_rows", launch_rows(st, t1, d->ncols, d->nrows, sm, t0)) ||
           launched(c, "k_cols", launch_cols(st, t0, d->ncols, d->nrows, sm, L0.img)))
         return -1;
     } else {
-      if (launched(c, "k_u8_to_f32", launch_u8_to_f32(st, src, pitch, d->ncols, d->nrows, L0.img))) return -1;
+      if (launched(c, "k_u8_to_f32", to_f32(st, src, pitch, d->ncols, d->nrows, fmt, L0.img))) return -1;
     }
   }
   for (int l = 1; l < d->nlevels; ++l) {
@@ -95,7 +101,7 @@ DefTaps default_taps(const klt_hip_pyr_desc *d) {
 int launch_l0(klt_hip_ctx *c, hipStream_t st, const uint8_t *src, long pitch, long stride, int W, int H,
               const DefTaps &T, int vec_u8, int vec_out, float *img, float *gx, float *gy, float *hs, int W1,
               int do_hs, long fs0, long fsh, int F, int &r0, int &r1, int *p0 = nullptr, int *p1 = nullptr,
-              int il = 0) {
+              int il = 0, int fmt = KLT_HIP_FRAME_GRAY8) {
   if (r1 <= r0 || F <= 0) return 0;
   const int TH = geom::L0_TH;
   const int nty = (H + TH - 1) / TH;
@@ -111,7 +117,7 @@ int launch_l0(klt_hip_ctx *c, hipStream_t st, const uint8_t *src, long pitch, lo
     *p1 = py1 >= nty ? H : py1 * TH;
   }
   return launched(c, "k_pyr_l0", launch_pyr_l0(st, src, (int)pitch, stride, W, H, T, vec_u8, vec_out, img, gx, gy,
-                                               hs, W1, do_hs, fs0, fsh, F, ty0, ty1, py0, py1, il));
+                                               hs, W1, do_hs, fs0, fsh, F, ty0, ty1, py0, py1, il, fmt));
 }
 
 // KLT_L1_THIN=0: a single frame's level 1 in 32-row tiles too (A/B)
@@ -124,7 +130,7 @@ bool l1_thin() {
 }
 
 int build_fused(klt_hip_ctx *c, int s, const klt_hip_pyr_desc *d, const uint8_t *src, long pitch,
-                hipStream_t st) {
+                hipStream_t st, int fmt) {
   Slot &S = c->slot[s];
   const int W = d->ncols, H = d->nrows;
   const DefTaps T = default_taps(d);
@@ -133,13 +139,13 @@ int build_fused(klt_hip_ctx *c, int s, const klt_hip_pyr_desc *d, const uint8_t 
   for (int l = 0; l < d->nlevels; ++l) S.lv[l].il = 1;  // interleaved
   if (two && grow(c, &c->d_hs, &c->hs_cap, (size_t)hs_size(W1 > 0 ? W1 : 1, H))) return -1;
   if ((long)W * H == 0) return 0;
-  const int vec_u8 = (W % 4 == 0 && W >= 16 && pitch % 4 == 0 && ((uintptr_t)src & 3) == 0) ? 1 : 0;
+  const int vec_u8 = vec_u8_ok(src, pitch, 0L, W);
   const int vec_out = (W % 4 == 0) ? 1 : 0;
   {
     TimedScope ts(c, T_L0, st);
     int r0 = 0, r1 = H;
     if (launch_l0(c, st, src, pitch, 0L, W, H, T, vec_u8, vec_out, S.lv[0].img, S.lv[0].gx, S.lv[0].gy, c->d_hs,
-                  W1, (two && W1 > 0) ? 1 : 0, 0L, 0L, 1, r0, r1, nullptr, nullptr, 1))
+                  W1, (two && W1 > 0) ? 1 : 0, 0L, 0L, 1, r0, r1, nullptr, nullptr, 1, fmt))
       return -1;
   }
   if (two && (long)W1 * H1 > 0) {
@@ -316,8 +322,7 @@ int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const u
   const bool two = d->nlevels == 2;
   const int W1 = two ? K.lv[1].w : 0, H1 = two ? K.lv[1].h : 0;
   if ((long)W * H == 0 || F <= 0) return 0;
-  const int vec_u8 =
-      (W % 4 == 0 && W >= 16 && pitch % 4 == 0 && stride % 4 == 0 && ((uintptr_t)src & 3) == 0) ? 1 : 0;
+  const int vec_u8 = vec_u8_ok(src, pitch, stride, W);
   const int vec_out = (W % 4 == 0) ? 1 : 0;
   const long fs0 = (long)W * H, fsh = hs_size(W1, H), fs1 = (long)W1 * H1;
   int r0 = clampi(row_lo, 0, H), r1 = row_hi >= H ? H : clampi(row_hi, r0, H);
@@ -334,7 +339,7 @@ int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const u
     const long o0 = first * np0 * fs0;
     if (launch_l0(c, st, src, pitch, stride, W, H, T, vec_u8, vec_out, K.lv[0].img + o0, K.lv[0].gx + o0,
                   K.lv[0].gy + o0, K.hs + first * fsh, W1, (two && W1 > 0) ? 1 : 0, step * np0 * fs0, step * fsh, F, r0,
-                  r1, &p0, &p1, il))
+                  r1, &p0, &p1, il, c->frame_format))
       return -1;
   }
   K.vlo[0] = p0;
@@ -394,11 +399,14 @@ int build_pyramid_on(klt_hip_ctx *c, int s, const klt_hip_pyr_desc *d, const uns
     src = c->d_u8[buf];
     pitch = d->ncols;
   }
-  if (pitch < d->ncols) return fail(c, "build_pyramid: pitch %ld < ncols %d", pitch, d->ncols);
+  // a caller's device frame holds the context's pixels; a staging buffer is gray
+  const int fmt = frame ? c->frame_format : KLT_HIP_FRAME_GRAY8;
+  if (pitch < (long)d->ncols * frame_bpp(fmt))
+    return fail(c, "build_pyramid: pitch %ld < ncols %d * %d bytes per pixel", pitch, d->ncols, frame_bpp(fmt));
   if (ensure_slot(c, s, d)) return -1;
   const bool fz = fused_ok(d) && !c->force_generic;
   c->slot[s].fused = fz ? 1 : 0;
-  return fz ? build_fused(c, s, d, src, pitch, st) : build_generic(c, s, d, src, pitch, st);
+  return fz ? build_fused(c, s, d, src, pitch, st, fmt) : build_generic(c, s, d, src, pitch, st, fmt);
 }
 
 KLT_API int klt_hip_fused_path(klt_hip_ctx *c, const klt_hip_pyr_desc *d) {
@@ -446,4 +454,53 @@ KLT_API int klt_hip_download_level(klt_hip_ctx *c, int s, int l, int which, floa
   HIPCHK(c, hipMemcpyAsync(host, p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// pixel formats of device frames (klt_hip.h, "Pixel format of DEVICE frames")
+// ---------------------------------------------------------------------------
+KLT_API int klt_hip_frame_bpp(int format) { return frame_bpp(format); }
+
+KLT_API int klt_hip_set_frame_format(klt_hip_ctx *c, int format) {
+  if (!c) return -1;
+  if (frame_bpp(format) < 0)
+    return fail(c, "set_frame_format: unknown format %d (KLT_HIP_FRAME_GRAY8 .. KLT_HIP_FRAME_BGRA8)", format);
+  c->frame_format = format;
+  return 0;
+}
+
+KLT_API int klt_hip_get_frame_format(klt_hip_ctx *c) { return c ? c->frame_format : -1; }
+
+KLT_API int klt_hip_gray_host(int format, const unsigned char *src, long pitch, int ncols, int nrows,
+                              unsigned char *dst, long dst_pitch) {
+  const int bpp = frame_bpp(format);
+  if (bpp < 0 || !src || !dst || ncols < 0 || nrows < 0 || pitch < (long)ncols * bpp || dst_pitch < ncols) return -1;
+  const bool bgr = frame_bgr(format);
+  for (int y = 0; y < nrows; ++y) {
+    const unsigned char *s = src + (long)y * pitch;
+    unsigned char *o = dst + (long)y * dst_pitch;
+    if (bpp == 1) {
+      memmove(o, s, (size_t)ncols);
+      continue;
+    }
+    for (int x = 0; x < ncols; ++x, s += bpp) o[x] = (unsigned char)gray_of(s[0], s[1], s[2], bgr);
+  }
+  return 0;
+}
+
+KLT_API int klt_hip_to_gray(klt_hip_ctx *c, int format, const unsigned char *dev_src, long pitch, long stride,
+                            int nframes, int ncols, int nrows, unsigned char *dev_dst, long dst_pitch,
+                            long dst_stride) {
+  if (!c) return fail(c, "to_gray: null context");
+  const int bpp = frame_bpp(format);
+  if (bpp < 0) return fail(c, "to_gray: unknown format %d", format);
+  if (nframes < 0 || ncols < 0 || nrows < 0) return fail(c, "to_gray: bad nframes/ncols/nrows");
+  if (nframes == 0 || (long)ncols * nrows == 0) return 0;
+  if (!dev_src || !dev_dst) return fail(c, "to_gray: null frames");
+  if (pitch < (long)ncols * bpp)
+    return fail(c, "to_gray: pitch %ld < ncols %d * %d bytes per pixel", pitch, ncols, bpp);
+  if (dst_pitch < ncols) return fail(c, "to_gray: dst_pitch %ld < ncols %d", dst_pitch, ncols);
+  if (use_device(c)) return -1;
+  return launched(c, "k_to_gray", launch_to_gray(c->stream, format, dev_src, pitch, stride, nframes, ncols, nrows,
+                                                 dev_dst, dst_pitch, dst_stride));
 }

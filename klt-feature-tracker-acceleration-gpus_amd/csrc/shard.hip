@@ -732,6 +732,8 @@ KLT_API int klt_shard_track(klt_shard *s, const klt_hip_pyr_desc *pd, const klt_
   if (pd->nrows != s->nrows) return sfail(s, "shard_track: frames have %d rows, the shard %d", pd->nrows, s->nrows);
   if (n < 0 || nframes < 1 || !frames || (n > 0 && (!x || !y || !val)))
     return sfail(s, "shard_track: bad frames or feature arrays");
+  if (klt_hip_get_frame_format(s->ctx) != KLT_HIP_FRAME_GRAY8)
+    return sfail(s, "shard_track: colour frames are not covered (klt_hip_set_frame_format); convert with klt_hip_to_gray");
   DeviceGuard guard;
   if (hipSetDevice(klt_hip_ctx_device(s->ctx)) != hipSuccess) return abort_comm(s, "shard_track: device");
   hipStream_t st = (hipStream_t)klt_hip_get_stream(s->ctx);
@@ -801,6 +803,8 @@ KLT_API int klt_shard_eigen(klt_shard *s, const klt_hip_pyr_desc *pd, const klt_
                             int *dev_map, klt_shard_frames_fn full, void *user) {
   if (!s || !pd || !sd || !dev_map) return sfail(s, "shard_eigen: null argument");
   if (pd->nrows != s->nrows) return sfail(s, "shard_eigen: frames have %d rows, the shard %d", pd->nrows, s->nrows);
+  if (klt_hip_get_frame_format(s->ctx) != KLT_HIP_FRAME_GRAY8)
+    return sfail(s, "shard_eigen: colour frames are not covered (klt_hip_set_frame_format); convert with klt_hip_to_gray");
   DeviceGuard guard;
   if (hipSetDevice(klt_hip_ctx_device(s->ctx)) != hipSuccess) return sfail(s, "shard_eigen: device");
   int lo, hi, nx, ny, j0, j1;

@@ -14,6 +14,8 @@ MAX_LEVELS = 8
 EXACT, FAST = 0, 1
 FB_REJECTED = -6  # KLT_HIP_FB_REJECTED: lost to the forward-backward check (klt_hip_set_fb)
 MAX_SEQUENCES = 64  # KLT_HIP_MAX_SEQUENCES: klt_hip_track_frames_multi's nseq
+# KLT_HIP_FRAME_*: the pixels of device frames (klt_hip_set_frame_format)
+FRAME_GRAY8, FRAME_RGB8, FRAME_BGR8, FRAME_RGBA8, FRAME_BGRA8 = range(5)
 
 
 class Taps(C.Structure):
@@ -93,6 +95,12 @@ DEVICE_PROTOS = {
     "klt_hip_current_device": (C.c_int, []),
     "klt_hip_upload_frame": (C.c_int, [V, C.c_int, V, C.c_int, C.c_int]),
     "klt_hip_build_pyramid": (C.c_int, [V, C.c_int, C.POINTER(PyrDesc), V, C.c_long, C.c_int]),
+    "klt_hip_frame_bpp": (C.c_int, [C.c_int]),
+    "klt_hip_set_frame_format": (C.c_int, [V, C.c_int]),
+    "klt_hip_get_frame_format": (C.c_int, [V]),
+    "klt_hip_gray_host": (C.c_int, [C.c_int, V, C.c_long, C.c_int, C.c_int, V, C.c_long]),
+    "klt_hip_to_gray": (C.c_int, [V, C.c_int, V, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, V, C.c_long,
+                                  C.c_long]),
     "klt_hip_pyramid_path": (C.c_int, [V, C.c_int]),
     "klt_hip_fused_path": (C.c_int, [V, C.POINTER(PyrDesc)]),
     "klt_hip_set_track_order": (C.c_int, [V, C.c_int]),
