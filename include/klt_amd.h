@@ -103,6 +103,25 @@ void KLTTrackSequenceReplace(KLT_TrackingContext tc, KLT_PixelType **frames, int
 void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, int nseq, int nframes, int ncols, int nrows,
                        KLT_FeatureList *fl, KLT_FeatureTable *ft, int ft_col);
 
+/* KLTTrackSequenceReplace for nseq independent sequences of one geometry:
+     for (s = 0; s < nseq; s++)
+       KLTTrackSequenceReplace(tc_s, frames[s], nframes, ncols, nrows, fl[s], ft ? ft[s] : NULL, ft_col, every);
+   on nseq fresh copies tc_s of tc, with bit-identical lists (the aff_* fields
+   of replaced slots included) and tables.  The sequences are tracked together
+   as in KLTTrackSequences, and at every `every`-th tracked frame the lost
+   features of every sequence are replaced inside the device call
+   (klt_hip_track_frames_multi_replace, with the frames tracked so far as its
+   count0: the groups of 16 frames do not show): one trackability-map launch
+   serves all sequences that lost a feature, the selections run one sequence
+   after the other.  every < 1 is a KLTError, raised before any device is
+   touched; with every > nframes - 1 it is KLTTrackSequences.  A negative
+   tc->mindist gets the reference's warning once (tc itself is left as it is:
+   the loop changes its copies).  It runs exactly the loop above where
+   KLTTrackSequences would fall back to its loop, and when tc->sequentialMode
+   is off (KLTTrackSequenceReplace then runs its per-frame loop). */
+void KLTTrackSequencesReplace(KLT_TrackingContext tc, KLT_PixelType ***frames, int nseq, int nframes, int ncols,
+                              int nrows, KLT_FeatureList *fl, KLT_FeatureTable *ft, int ft_col, int every);
+
 /* host side of the synthetic generator (include/klt_synth.h) */
 void klt_synth_frame(uint64_t seed, int t, int ncols, int nrows, unsigned char *out);
 /* the reference quicksort's permutation on {val, idx} pairs (test hook) */

@@ -675,7 +675,9 @@ const char *klt_hip_eigen_kernel(klt_hip_ctx *ctx);
    lost and gets replaced; klt_hip_set_fb_table rows are unchanged).
    Failing with -1 and a message before any launch, arrays untouched, while it
    is on: klt_hip_track_frames_band, klt_hip_track_frames_multi,
-   klt_hip_track_sequence, and any call with klt_hip_set_frames_affine on.
+   klt_hip_track_frames_multi_replace (which takes its replacement as an
+   argument), klt_hip_track_sequence, and any call with
+   klt_hip_set_frames_affine on.
    klt_hip_set_frames_replace(NULL) turns it off, and so does
    klt_hip_ctx_reset; turning it on zeroes the three counters of
    klt_hip_get_frames_replace (frames tracked, replacements run -- those with
@@ -694,6 +696,61 @@ int klt_hip_get_frames_replace(klt_hip_ctx *ctx, int *on, long *frames, long *re
    feature or NOT_FOUND) since the setting was turned on, else 0: the slots
    whose affine fields a klt.h caller resets (KLTTrackSequenceReplace) */
 int klt_hip_frames_replace_changed(klt_hip_ctx *ctx, unsigned char *changed, int n);
+
+/* klt_hip_track_frames_multi with lost features replaced inside the call: for
+   every sequence s the list, the table rows, the marks and the counters are,
+   byte for byte, what
+       klt_hip_frames_begin(frame 0 of s); klt_hip_set_frames_replace(rep);
+       klt_hip_track_frames(frames 1..nframes of s)
+   gives on a context of its own.  Frames, banks, coverage
+   (klt_hip_multi_covers), argument checks and frame formats are
+   klt_hip_track_frames_multi's.  The replacement is an argument, not a
+   setting: the multi call keeps no state from call to call.  A replacement is
+   due after tracked frame j (1-based within the call) when
+   (count0 + j) % rep->every == 0; count0 is the number of frames tracked
+   before this call, so a sequence split over several calls gives the bytes of
+   one call.  A replacement due at the call's last frame is run.  It does to
+   each sequence, on its own list and its own frame j, what
+   klt_hip_set_frames_replace describes: nothing, counters included, when none
+   of its slots is lost; otherwise its lost slots are filled from the
+   trackability map of its frame, its live features blocking their squares,
+   and the slots that cannot be filled become (-1, -1, KLT_NOT_FOUND).  No
+   sequence sees another's features or map.  Table row j-1 carries every list
+   after the replacement.  changed (host, n bytes, optional; the caller zeroes
+   it): changed[k] |= 1 for every slot written.  runs / filled (host, nseq
+   longs each, optional): added to, per sequence, the replacements run -- those
+   with a lost slot -- and the slots filled.
+   Schedule: the pyramid launches keep the chunk; the tracker launch alone is
+   cut at the replacement frames, for all sequences at once.  At a cut the n
+   features of x | y | val come to pinned host memory (one transfer when
+   y == x + n and val == y + n, else three), the next chunk's pyramids are
+   queued before the host waits, the sequences with a lost slot get their maps
+   from one k_min_eigen7_multi launch (a 7x7 window with step <= 2; any other
+   description from one k_min_eigen launch per sequence), and
+   klt_hip_select_dev_map runs per sequence, one after the other; the lists and
+   the table row go back when anything was written.  The call returns with the
+   work after its last cut still queued, like klt_hip_track_frames_multi.
+   Refused with -1 and a message before any launch, arrays untouched:
+   everything klt_hip_track_frames_multi refuses, rep == NULL, the descriptions
+   klt_hip_set_frames_replace refuses, count0 < 0, and the context's own
+   klt_hip_set_frames_replace setting being on (it belongs to the
+   single-sequence calls). */
+int klt_hip_track_frames_multi_replace(klt_hip_ctx *ctx, const klt_hip_pyr_desc *pdesc,
+                                       const klt_hip_track_desc *tdesc, const klt_hip_replace_desc *rep, long count0,
+                                       const unsigned char *frames, long pitch, long stride, long seq_stride, int nseq,
+                                       int nframes, int chunk, const int *n_seq, float *x, float *y, int *val,
+                                       float *tab_x, float *tab_y, int *tab_val, long tab_stride,
+                                       unsigned char *changed, long *runs, long *filled);
+/* test hook: the trackability maps of nsel (1..KLT_HIP_MAX_SEQUENCES) frames of
+   level-0 records in device memory ({gx, gy, img} per pixel, ncols x nrows,
+   frame f at dev_rec + f*frame_stride floats -- what a multi bank holds) by
+   one k_min_eigen7_multi launch: which (host, nsel frame indices, any subset
+   in any order) picks the frames, map i goes to dev_maps + i*nx*ny.  Each map
+   is bit for bit klt_hip_min_eigen's of that frame.  Synchronous.  Returns -1
+   with a message for a window other than 7x7, a step (nSkippedPixels + 1)
+   outside 1..2, a border below 3, or nsel out of range. */
+int klt_hip_min_eigen_records(klt_hip_ctx *ctx, const float *dev_rec, long frame_stride, const int *which, int nsel,
+                              int ncols, int nrows, const klt_hip_select_desc *desc, int *dev_maps);
 
 /* the host half of KLTReplaceLostFeatures (selectGoodFeatures.c:514-541 ->
    _KLTSelectGoodFeatures' sort and minimum-distance fill, :425-453) over a

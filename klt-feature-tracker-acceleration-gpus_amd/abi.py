@@ -119,6 +119,9 @@ AMD_KLT_PROTOS = {
     # frames[s][f]; fl[s]; ft: NULL or ft[s] (each may be NULL)
     "KLTTrackSequences": (None, [TC, C.POINTER(C.POINTER(U8P)), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FL),
                                  C.POINTER(FT), C.c_int]),
+    # ..., ft_col, every
+    "KLTTrackSequencesReplace": (None, [TC, C.POINTER(C.POINTER(U8P)), C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(FL), C.POINTER(FT), C.c_int, C.c_int]),
 }
 
 

@@ -1245,8 +1245,11 @@ static KLT_TrackingContext fresh_copy(KLT_TrackingContext tc)
 #define MULTI_STAGE_BYTES ((size_t)256 << 20) /* pinned staging of one group of frames, at most */
 enum { MEMCPY_H2D = 1, MEMCPY_D2H = 2 };      /* klt_hip_memcpy's kinds (hipMemcpyKind) */
 
-EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, int nseq, int nframes, int ncols,
-                              int nrows, KLT_FeatureList *fl, KLT_FeatureTable *ft, int ft_col)
+/* every == 0: KLTTrackSequences; every >= 1: KLTTrackSequencesReplace, the same
+   call with KLTReplaceLostFeatures after every `every`-th tracked frame of
+   each sequence (klt_hip_track_frames_multi_replace) */
+static void track_sequences(KLT_TrackingContext tc, KLT_PixelType ***frames, int nseq, int nframes, int ncols,
+                            int nrows, KLT_FeatureList *fl, KLT_FeatureTable *ft, int ft_col, int every)
 {
   klt_ctx_full *f = FULL(tc);
   klt_hip_ctx *dev = NULL;
@@ -1255,6 +1258,8 @@ EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, i
   taps_state st, after1;
   const int T = nframes - 1;
   int s, k, j, j0, n = 0, F, multi, any_ft = 0, pinned;
+  klt_hip_replace_desc rd;
+  unsigned char *changed = NULL;
   int *counts, *hv, *tv = NULL;
   float *hx, *hy, *tx = NULL, *ty = NULL;
   unsigned char *stage, *dfr;
@@ -1263,6 +1268,7 @@ EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, i
   size_t fb, stage_bytes;
 
   if (nseq < 1 || nframes < 2) return;
+  if (every > T) every = 0; /* no replacement falls inside the sequences */
   window_fix(tc, NULL);
   affine_check_tc(tc);
   for (s = 0; s < nseq; s++) {
@@ -1281,6 +1287,8 @@ EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, i
      description: the dry run of its kernel-cache lookups, sequence after
      sequence as the loop would make them */
   multi = nseq <= KLT_HIP_MAX_SEQUENCES && tc->affineConsistencyCheck < 0 && !f->fb_on && !tc->writeInternalImages;
+  /* the batched replacement reads the tracked frame's own pyramid: sequential mode only (track_sequence) */
+  if (every && !tc->sequentialMode) multi = 0;
   pthread_mutex_lock(&g_taps_lock);
   st = g_taps;
   pthread_mutex_unlock(&g_taps_lock);
@@ -1298,22 +1306,45 @@ EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, i
   }
   if (multi) {
     dev = device_of(tc);
-    apply_fb(tc, "KLTTrackSequences");
+    apply_fb(tc, every ? "KLTTrackSequencesReplace" : "KLTTrackSequences");
     klt_amd_track_desc(tc, &td);
     multi = klt_hip_multi_covers(dev, &D, &td) == 1;
   }
   if (!multi) {
     for (s = 0; s < nseq; s++) {
       KLT_TrackingContext t = fresh_copy(tc);
-      KLTTrackSequence(t, frames[s], nframes, ncols, nrows, fl[s], ft ? ft[s] : NULL, ft_col);
+      if (every)
+        KLTTrackSequenceReplace(t, frames[s], nframes, ncols, nrows, fl[s], ft ? ft[s] : NULL, ft_col, every);
+      else
+        KLTTrackSequence(t, frames[s], nframes, ncols, nrows, fl[s], ft ? ft[s] : NULL, ft_col);
       KLTFreeTrackingContext(t);
     }
     return;
   }
   if (KLT_verbose >= 1) {
-    fprintf(stderr, "(KLT) Tracking %d sequences of %d %d by %d frames, %d features in all...  ", nseq, T, ncols, nrows,
-            n);
+    fprintf(stderr, "(KLT) Tracking %d sequences of %d %d by %d frames, %d features in all", nseq, T, ncols, nrows, n);
+    if (every) fprintf(stderr, ", replacing lost features every %d", every);
+    fprintf(stderr, "...  ");
     fflush(stderr);
+  }
+  if (every) {
+    int mindist = tc->mindist;
+    if (mindist < 0) { /* once, not once per sequence; tc itself stays as the loop on fresh copies leaves it */
+      KLTWarning("(_KLTSelectGoodFeatures) Tracking context field tc->mindist is negative (%d); "
+                 "setting to zero",
+                 mindist);
+      mindist = 0;
+    }
+    rd.sel.window_width = tc->window_width;
+    rd.sel.window_height = tc->window_height;
+    rd.sel.borderx = tc->borderx < tc->window_width / 2 ? tc->window_width / 2 : tc->borderx;
+    rd.sel.bordery = tc->bordery < tc->window_height / 2 ? tc->window_height / 2 : tc->bordery;
+    rd.sel.nSkippedPixels = tc->nSkippedPixels;
+    rd.mindist = mindist;
+    rd.min_eigenvalue = tc->min_eigenvalue;
+    rd.every = every;
+    changed = (unsigned char *)calloc((size_t)n + 1, 1);
+    if (!changed) KLTError("(KLTTrackSequencesReplace) Out of memory");
   }
 
   /* groups of F tracked frames: frame-major in pinned staging (the group's
@@ -1337,9 +1368,10 @@ EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, i
     KLTError("(KLTTrackSequences) Out of memory");
   pinned = stage_bytes > 0 && klt_hip_register_host(dev, stage, stage_bytes) == 0; /* pageable still works */
   dfr = (unsigned char *)klt_hip_malloc(dev, stage_bytes);
-  dx = (float *)klt_hip_malloc(dev, sizeof(float) * (n + 1));
-  dy = (float *)klt_hip_malloc(dev, sizeof(float) * (n + 1));
-  dv = (int *)klt_hip_malloc(dev, sizeof(int) * (n + 1));
+  /* x | y | val in one block: a replacement moves the lists in one transfer each way */
+  dx = (float *)klt_hip_malloc(dev, sizeof(float) * ((size_t)3 * n + 1));
+  dy = dx ? dx + n : NULL;
+  dv = dx ? (int *)(dy + n) : NULL;
   if (any_ft) {
     dtx = (float *)klt_hip_malloc(dev, sizeof(float) * ((size_t)F * n + 1));
     dty = (float *)klt_hip_malloc(dev, sizeof(float) * ((size_t)F * n + 1));
@@ -1371,8 +1403,12 @@ EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, i
       const int fmt = klt_hip_get_frame_format(dev);
       int rc;
       klt_hip_set_frame_format(dev, KLT_HIP_FRAME_GRAY8);
-      rc = klt_hip_track_frames_multi(dev, &D, &td, dfr, ncols, (long)(nseq * fb), (long)fb, nseq, nf, nf, counts, dx,
-                                      dy, dv, dtx, dty, dtv, n);
+      if (every) /* j0 frames tracked so far: the replacement count runs on through the groups */
+        rc = klt_hip_track_frames_multi_replace(dev, &D, &td, &rd, j0, dfr, ncols, (long)(nseq * fb), (long)fb, nseq,
+                                                nf, nf, counts, dx, dy, dv, dtx, dty, dtv, n, changed, NULL, NULL);
+      else
+        rc = klt_hip_track_frames_multi(dev, &D, &td, dfr, ncols, (long)(nseq * fb), (long)fb, nseq, nf, nf, counts,
+                                        dx, dy, dv, dtx, dty, dtv, n);
       klt_hip_set_frame_format(dev, fmt);
       dev_check(tc, rc, "sequences: tracking");
     }
@@ -1397,20 +1433,26 @@ EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, i
   } else {
     dev_check(tc, klt_hip_sync(dev), "sequences: end");
   }
-  for (s = 0, k = 0; s < nseq; s++)
-    for (j = 0; j < counts[s]; j++, k++) {
+  for (s = 0, k = 0; s < nseq; k += counts[s], s++) {
+    /* a slot lost on entry that no replacement wrote stays untouched (:1346);
+       a written one got mark_found's treatment when it was written (track_sequence) */
+    unsigned char *skip = (unsigned char *)malloc((size_t)counts[s] + 1);
+    if (!skip) KLTError("(KLTTrackSequences) Out of memory");
+    for (j = 0; j < counts[s]; j++) skip[j] = fl[s]->feature[j]->val < 0 && !(changed && changed[k + j]);
+    if (changed) klt_select_apply(fl[s], hx + k, hy + k, hv + k, changed + k);
+    for (j = 0; j < counts[s]; j++) {
       KLT_Feature ftr = fl[s]->feature[j];
-      if (ftr->val < 0) continue; /* untouched, like the reference (:1346) */
-      ftr->x = hx[k];
-      ftr->y = hy[k];
-      ftr->val = hv[k];
-      if (hv[k] != KLT_TRACKED) drop_affine(ftr);
+      if (skip[j]) continue;
+      ftr->x = hx[k + j];
+      ftr->y = hy[k + j];
+      ftr->val = hv[k + j];
+      if (hv[k + j] != KLT_TRACKED) drop_affine(ftr);
     }
+    free(skip);
+  }
   if (pinned) klt_hip_unregister_host(dev, stage);
   klt_hip_free(dev, dfr);
   klt_hip_free(dev, dx);
-  klt_hip_free(dev, dy);
-  klt_hip_free(dev, dv);
   klt_hip_free(dev, dtx);
   klt_hip_free(dev, dty);
   klt_hip_free(dev, dtv);
@@ -1422,6 +1464,7 @@ EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, i
   free(tx);
   free(ty);
   free(tv);
+  free(changed);
 
   /* the kernel cache ends where the loop would leave it */
   pthread_mutex_lock(&g_taps_lock);
@@ -1433,6 +1476,20 @@ EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, i
     fprintf(stderr, "\n\t%d features successfully tracked.\n", left);
     fflush(stderr);
   }
+}
+
+EXPORT void KLTTrackSequences(KLT_TrackingContext tc, KLT_PixelType ***frames, int nseq, int nframes, int ncols,
+                              int nrows, KLT_FeatureList *fl, KLT_FeatureTable *ft, int ft_col)
+{
+  track_sequences(tc, frames, nseq, nframes, ncols, nrows, fl, ft, ft_col, 0);
+}
+
+/* KLTTrackSequenceReplace for nseq independent sequences (klt_amd.h) */
+EXPORT void KLTTrackSequencesReplace(KLT_TrackingContext tc, KLT_PixelType ***frames, int nseq, int nframes, int ncols,
+                                     int nrows, KLT_FeatureList *fl, KLT_FeatureTable *ft, int ft_col, int every)
+{
+  if (every < 1) KLTError("(KLTTrackSequencesReplace) every=%d: expected at least 1", every);
+  track_sequences(tc, frames, nseq, nframes, ncols, nrows, fl, ft, ft_col, every);
 }
 
 /* ------------------------------------------------------------------ */

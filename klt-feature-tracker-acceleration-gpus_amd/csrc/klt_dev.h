@@ -209,6 +209,13 @@ struct TrkMultiArgs {
   int nseq;
   int first[kMaxSeq + 1];
 };
+// the trackability maps of several of those pyramids in one launch
+// (k_min_eigen7_multi): map i is taken from pyramid seq[i] of the group, by
+// value like TrkMultiArgs -- no device table, no upload
+struct EigMultiArgs {
+  int nsel;
+  int seq[kMaxSeq];
+};
 constexpr int kCountSlots = 64;  // counter pairs (the host sums them)
 constexpr int kProfN = 12;       // instrumented build: counters per wave
 
@@ -303,6 +310,12 @@ struct GradTaps {
 };
 hipError_t launch_min_eigen_img(hipStream_t st, const float *img, int W, int H, const GradTaps &t, int bx, int by,
                                 int step, int nx, int ny, int *out, const char **name = nullptr);
+// the same map (7x7 window, step 1 or 2, borders >= 3) of m.nsel frames of full
+// {gx, gy, img} records, frame m.seq[i] at rec + m.seq[i] * frame_stride
+// (floats), in one launch: map i at maps + i * nx * ny, each bit for bit
+// launch_min_eigen's for that frame
+hipError_t launch_min_eigen_multi(hipStream_t st, const float *rec, long frame_stride, const EigMultiArgs &m, int W,
+                                  int bx, int by, int step, int nx, int ny, int *maps, const char **name = nullptr);
 hipError_t launch_synth(hipStream_t st, unsigned long long seed, int t0, int n, int W, int H, int row0, uint8_t *out,
                         long pitch, long fstride);
 hipError_t launch_selftest_sqrt(const double *in, double *out, int n);

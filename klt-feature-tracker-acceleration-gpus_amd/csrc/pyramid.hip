@@ -11,6 +11,7 @@
 //   k_to_gray             colour frames to gray frames (klt_hip_to_gray)
 //   k_min_eigen           the trackability map (selectGoodFeatures.c:375-424);
 //   k_min_eigen7_img      the same from a level-0 img plane alone
+//   k_min_eigen7_multi    the maps of several frames of records in one launch
 //   k_synth               synthetic frames (include/klt_synth.h)
 //
 // Parity contract: every output is bit-identical to the reference CPU path
@@ -1175,6 +1176,45 @@ __global__ __launch_bounds__(256) void k_min_eigen7(const float *__restrict__ gx
   eig_tile_sums<STEP>(gq, gm, ix0, iy0, nx, ny, out);
 }
 
+// The same map for several frames of one geometry in one launch
+// (klt_hip_track_frames_multi_replace): blockIdx.x is a tile of one map as in
+// k_min_eigen7, blockIdx.y picks the frame -- full {gx, gy, img} records at
+// rec + m.seq[blockIdx.y] * frame_stride, the multi banks' level 0 -- and map
+// blockIdx.y goes to maps + blockIdx.y * nx * ny.  The staging and the sums
+// are k_min_eigen7's with the records' pixel stride, so every map is bit for
+// bit what k_min_eigen7 gives for that frame.
+template <int STEP>
+__global__ __launch_bounds__(256) void k_min_eigen7_multi(const float *__restrict__ rec, long frame_stride,
+                                                         EigMultiArgs m, int W, int bx, int by, int nx, int ny,
+                                                         int *__restrict__ maps) {
+  using namespace eig;
+  constexpr int step = STEP, C = (TX - 1) * STEP + WIN, R = (TY - 1) * STEP + WIN, C_MAX = C;
+  __shared__ f2 gq[R * C];
+  __shared__ float gm[R * C];
+  const float *__restrict__ g = rec + (long)m.seq[blockIdx.y] * frame_stride;
+  int *__restrict__ out = maps + (long)blockIdx.y * ((long)nx * ny);
+  const int tiles_x = (nx + TX - 1) / TX;
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
+  const int ix0 = tx * TX, iy0 = ty * TY;
+  const int x0 = bx + ix0 * step - HW, y0 = by + iy0 * step - HW;
+  const int xmax = bx + (nx - 1) * step + HW, ymax = by + (ny - 1) * step + HW;
+#pragma unroll
+  for (int p0 = 0; p0 < R * C; p0 += 256) {
+    const int p = p0 + (int)threadIdx.x;
+    if (p >= R * C) break;
+    const int r = p / C, c = p - r * C;
+    const int yy = min(y0 + r, ymax), xx = min(x0 + c, xmax);
+    const long o = ((long)yy * W + xx) * kRec;
+    const float a = g[o + kRecGx], b = g[o + kRecGy];
+    const f2 ab = {a, b};
+    const f2 sq = ab * ab;
+    gq[r * C_MAX + c] = sq;
+    gm[r * C_MAX + c] = a * b;
+  }
+  __syncthreads();
+  eig_tile_sums<STEP>(gq, gm, ix0, iy0, nx, ny, out);
+}
+
 // The same map from a level-0 img plane alone (row stride W): what an
 // image-only bank frame holds (klt_hip_set_lazy_grad).  The workgroup stages
 // its image tile with a halo of kRG (gradient) + HW (window) pixels, forms
@@ -1537,6 +1577,23 @@ hipError_t launch_min_eigen(hipStream_t st, const float *gx, const float *gy, in
   }
   hipLaunchKernelGGL(k_min_eigen, dim3(blocks_for(np)), dim3(kBlock), 0, st, gx, gy, W, ps, bx, by, step, nx, ny, hw,
                      hh, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_min_eigen_multi(hipStream_t st, const float *rec, long frame_stride, const EigMultiArgs &m, int W,
+                                  int bx, int by, int step, int nx, int ny, int *maps, const char **name) {
+  if ((long)nx * ny == 0 || m.nsel == 0) return hipSuccess;
+  if (step < 1 || step > eig::kMaxStep || m.nsel < 0 || m.nsel > kMaxSeq || bx < eig::HW || by < eig::HW)
+    return hipErrorInvalidValue;
+  if (name)
+    *name = step == 1 ? "kltdev::(anonymous namespace)::k_min_eigen7_multi<1>"
+                      : "kltdev::(anonymous namespace)::k_min_eigen7_multi<2>";
+  const long tiles = (long)((nx + eig::TX - 1) / eig::TX) * ((ny + eig::TY - 1) / eig::TY);
+  const dim3 grid((unsigned)tiles, (unsigned)m.nsel);
+  if (step == 1)
+    hipLaunchKernelGGL(k_min_eigen7_multi<1>, grid, dim3(256), 0, st, rec, frame_stride, m, W, bx, by, nx, ny, maps);
+  else
+    hipLaunchKernelGGL(k_min_eigen7_multi<2>, grid, dim3(256), 0, st, rec, frame_stride, m, W, bx, by, nx, ny, maps);
   return hipGetLastError();
 }
 

@@ -387,6 +387,23 @@ inline int launched(klt_hip_ctx *c, const char *what, hipError_t e) {
   return 0;
 }
 
+// the pinned list of a replacement inside a batched call (x | y | val of n
+// features at c->h_rep) and the event its download is waited for
+inline int ensure_rep_host(klt_hip_ctx *c, int n, hipStream_t st) {
+  if (c->h_rep_cap < (size_t)n || !c->h_rep) {
+    if (c->h_rep) {
+      HIPCHK(c, hipStreamSynchronize(st));  // no copy still uses the old block
+      HIPCHK(c, hipHostFree(c->h_rep));
+    }
+    c->h_rep = nullptr;
+    c->h_rep_cap = 0;
+    HIPCHK(c, hipHostMalloc((void **)&c->h_rep, 3 * sizeof(float) * (size_t)n, hipHostMallocDefault));
+    c->h_rep_cap = (size_t)n;
+  }
+  if (!c->ev_rep) HIPCHK(c, hipEventCreateWithFlags(&c->ev_rep, hipEventDisableTiming));
+  return 0;
+}
+
 // an entry point that tracks: the first tracker launch inside the outermost
 // one is the call's first (TrkAffArgs::fresh)
 struct AffCall {
@@ -445,6 +462,7 @@ int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const u
                      int plane_hi = 1 << 30, int il = 1, long first = 0, long step = 1);
 // runtime_frames.hip
 bool bank_fits(const Bank &K, const klt_hip_pyr_desc *d, int F);
+int replace_desc_refused(klt_hip_ctx *c, const klt_hip_replace_desc *d, const char *who);  // klt_hip_set_frames_replace's checks
 // runtime_track.hip
 int check_window(klt_hip_ctx *c, const klt_hip_track_desc *d);
 void fill_trk_args(const klt_hip_track_desc *d, int nlev, int ss, int ncols, int nrows, TrkArgs &a);

@@ -586,17 +586,7 @@ int replace_lost(klt_hip_ctx *c, const FramesCall &q, long row, Ahead ahead) {
   const int n = q.n;
   if (n <= 0) return ahead();
   hipStream_t st = c->stream;
-  if (c->h_rep_cap < (size_t)n || !c->h_rep) {
-    if (c->h_rep) {
-      HIPCHK(c, hipStreamSynchronize(st));  // no copy still uses the old block
-      HIPCHK(c, hipHostFree(c->h_rep));
-    }
-    c->h_rep = nullptr;
-    c->h_rep_cap = 0;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_rep, 3 * sizeof(float) * (size_t)n, hipHostMallocDefault));
-    c->h_rep_cap = (size_t)n;
-  }
-  if (!c->ev_rep) HIPCHK(c, hipEventCreateWithFlags(&c->ev_rep, hipEventDisableTiming));
+  if (ensure_rep_host(c, n, st)) return -1;
   float *hx = c->h_rep, *hy = hx + n;
   int *hv = reinterpret_cast<int *>(hy + n);
   const size_t nb = sizeof(float) * (size_t)n;
@@ -1061,18 +1051,23 @@ KLT_API int klt_hip_min_eigen_plane(klt_hip_ctx *c, const float *dev_img, int nc
   return 0;
 }
 
+int replace_desc_refused(klt_hip_ctx *c, const klt_hip_replace_desc *d, const char *who) {
+  if (d->every < 1) return fail(c, "%s: every %d < 1", who, d->every);
+  if (d->sel.window_width < 1 || d->sel.window_height < 1)
+    return fail(c, "%s: window %dx%d", who, d->sel.window_width, d->sel.window_height);
+  if (d->sel.borderx < d->sel.window_width / 2 || d->sel.bordery < d->sel.window_height / 2)
+    return fail(c, "%s: border smaller than window half size", who);
+  if (d->sel.nSkippedPixels < 0) return fail(c, "%s: bad nSkippedPixels", who);
+  return 0;
+}
+
 KLT_API int klt_hip_set_frames_replace(klt_hip_ctx *c, const klt_hip_replace_desc *d) {
   if (!c) return -1;
   if (!d) {
     c->rep_on = 0;
     return 0;
   }
-  if (d->every < 1) return fail(c, "set_frames_replace: every %d < 1", d->every);
-  if (d->sel.window_width < 1 || d->sel.window_height < 1)
-    return fail(c, "set_frames_replace: window %dx%d", d->sel.window_width, d->sel.window_height);
-  if (d->sel.borderx < d->sel.window_width / 2 || d->sel.bordery < d->sel.window_height / 2)
-    return fail(c, "set_frames_replace: border smaller than window half size");
-  if (d->sel.nSkippedPixels < 0) return fail(c, "set_frames_replace: bad nSkippedPixels");
+  if (replace_desc_refused(c, d, "set_frames_replace")) return -1;
   c->rep = *d;
   c->rep_on = 1;
   c->rep_frames = c->rep_runs = c->rep_filled = 0;

@@ -1,6 +1,6 @@
-// runtime_multi.hip -- host side of libklt_amd.so: the batched call over
-// several independent sequences (klt_hip_track_frames_multi; runtime.h).  No
-// kernels here.
+// runtime_multi.hip -- host side of libklt_amd.so: the batched calls over
+// several independent sequences (klt_hip_track_frames_multi,
+// klt_hip_track_frames_multi_replace; runtime.h).  No kernels here.
 //
 // One context, one stream.  The three banks of the plain batched calls are
 // laid out for nseq * chunk pyramids each and filled frame-major: pyramid
@@ -13,12 +13,20 @@
 // k_track7_multi launch over the concatenated lists.  Stream order is the
 // only dependency; the banks rotate all the same, so that a chunk never
 // overwrites the group it starts from.
+//
+// With a replacement description the tracker launch alone is cut, for all
+// sequences at once, after every frame at which a replacement is due: a
+// sub-launch over frames [f0, f1) of a bank starts from the group at f0 - 1.
+// At a cut the lists come to the host, the next chunk's pyramids are queued
+// before the host waits, the sequences with a lost slot get their maps from
+// one k_min_eigen7_multi launch over the adjacent pyramids of that frame, and
+// the selection engine fills each one's slots from its own map, one sequence
+// after the other.
 #include "runtime.h"
 
 namespace {
 // what the multi instances cover: the default configuration
-int multi_refused(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td) {
-  const char *who = "track_frames_multi";
+int multi_refused(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td, const char *who) {
   if (c->fb_on) return fail(c, "%s: the forward-backward check is not covered (klt_hip_set_fb)", who);
   if (c->aff_on) return fail(c, "%s: the affine check is not covered (klt_hip_set_frames_affine)", who);
   if (td->reduction != KLT_HIP_EXACT) return fail(c, "%s: needs KLT_HIP_EXACT sums", who);
@@ -33,20 +41,134 @@ int multi_refused(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_trac
                 "no klt_hip_set_prof buffer)", who);
   return 0;
 }
-}  // namespace
 
-KLT_API int klt_hip_multi_covers(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td) {
-  if (!c || !pd || !td) return fail(c, "multi_covers: null argument");
-  return multi_refused(c, pd, td) ? 0 : 1;
+// the replacement of klt_hip_track_frames_multi_replace: its description, the
+// frames tracked before the call and the caller's host arrays (optional)
+struct MultiReplace {
+  const klt_hip_replace_desc *d;
+  long count0;
+  unsigned char *changed;
+  long *runs, *filled;
+};
+
+struct MultiCall {
+  const klt_hip_pyr_desc *pd;
+  int nseq, n;
+  const TrkMultiArgs *ms;
+  float *x, *y;
+  int *val;
+  float *tab_x, *tab_y;
+  int *tab_val;
+  long tab_stride;
+};
+
+// n features of x | y | val between the device lists and the pinned block:
+// one transfer where the caller keeps the three arrays in one block
+int move_lists(klt_hip_ctx *c, const MultiCall &q, float *h, hipMemcpyKind kind, hipStream_t st) {
+  const size_t nb = sizeof(float) * (size_t)q.n;
+  const bool down = kind == hipMemcpyDeviceToHost;
+  if (q.y == q.x + q.n && reinterpret_cast<float *>(q.val) == q.y + q.n) {
+    HIPCHK(c, hipMemcpyAsync(down ? (void *)h : (void *)q.x, down ? (const void *)q.x : (const void *)h, 3 * nb, kind, st));
+    return 0;
+  }
+  void *dev[3] = {q.x, q.y, q.val};
+  for (int k = 0; k < 3; ++k) {
+    float *hk = h + (size_t)k * q.n;
+    HIPCHK(c, hipMemcpyAsync(down ? (void *)hk : dev[k], down ? (const void *)dev[k] : (const void *)hk, nb, kind, st));
+  }
+  return 0;
 }
 
-KLT_API int klt_hip_track_frames_multi(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td,
-                                       const unsigned char *frames, long pitch, long stride, long seq_stride,
-                                       int nseq, int nframes, int chunk, const int *n_seq, float *x, float *y,
-                                       int *val, float *tab_x, float *tab_y, int *tab_val, long tab_stride) {
-  const char *who = "track_frames_multi";
+// One replacement for every sequence (KLTReplaceLostFeatures in sequential
+// mode, each on its own list and its own frame): the frame just tracked is
+// group `group` of bank K, `row` its table row.  `ahead` queues whatever does
+// not depend on the lists before the host waits for them.
+template <class Ahead>
+int replace_lost_multi(klt_hip_ctx *c, const MultiCall &q, const MultiReplace &r, const Bank &K, long group, long row,
+                       Ahead ahead) {
+  const int n = q.n;
+  if (n <= 0) return ahead();
+  hipStream_t st = c->stream;
+  if (ensure_rep_host(c, n, st)) return -1;
+  float *hx = c->h_rep, *hy = hx + n;
+  int *hv = reinterpret_cast<int *>(hy + n);
+  if (move_lists(c, q, hx, hipMemcpyDeviceToHost, st)) return -1;
+  HIPCHK(c, hipEventRecord(c->ev_rep, st));
+  if (ahead()) return -1;
+  HIPCHK(c, hipEventSynchronize(c->ev_rep));
+  // the sequences with a lost slot: the others are left alone
+  EigMultiArgs m;
+  memset(&m, 0, sizeof m);
+  for (int s = 0; s < q.nseq; ++s) {
+    int lost = 0;
+    for (int k = q.ms->first[s]; k < q.ms->first[s + 1]; ++k) lost += hv[k] < 0;
+    if (lost) m.seq[m.nsel++] = s;
+  }
+  if (!m.nsel) return 0;
+  const klt_hip_select_desc &sd = r.d->sel;
+  const Level &L0 = K.lv[0];
+  const int hw = sd.window_width / 2, hh = sd.window_height / 2, step = sd.nSkippedPixels + 1;
+  const int cx = L0.w - 2 * sd.borderx, cy = L0.h - 2 * sd.bordery;
+  const int nx = cx > 0 ? (cx + step - 1) / step : 0, ny = cy > 0 ? (cy + step - 1) / step : 0;
+  const long np = (long)nx * ny, lfs = (long)L0.w * L0.h * kRec;
+  if (grow(c, &c->d_rep_map, &c->rep_map_cap, (size_t)(np * m.nsel))) return -1;
+  if (np > 0) {
+    const float *rec = L0.img + group * q.nseq * lfs;  // the frame's nseq adjacent pyramids
+    TimedScope ts(c, T_EIG, st);
+    if (hw == kRG && hh == kRG && step <= 2) {
+      if (launched(c, "k_min_eigen7_multi", launch_min_eigen_multi(st, rec, lfs, m, L0.w, sd.borderx, sd.bordery, step, nx,
+                                                                   ny, c->d_rep_map, &c->eig_kernel)))
+        return -1;
+    } else {  // not with the window the call covers; any other description: a launch per sequence
+      for (int i = 0; i < m.nsel; ++i) {
+        const float *g = rec + m.seq[i] * lfs;
+        if (launched(c, "k_min_eigen", launch_min_eigen(st, g + kRecGx, g + kRecGy, L0.w, kRec, sd.borderx, sd.bordery, step,
+                                                        nx, ny, hw, hh, c->d_rep_map + i * np, &c->eig_kernel)))
+          return -1;
+      }
+    }
+  }
+  std::vector<unsigned char> changed((size_t)n, 0);
+  long written = 0;
+  for (int i = 0; i < m.nsel; ++i) {
+    const int s = m.seq[i], a = q.ms->first[s], ns = q.ms->first[s + 1] - a;
+    if (klt_hip_select_dev_map(c, c->d_rep_map + i * np, nx, ny, &sd, L0.w, L0.h, r.d->mindist, r.d->min_eigenvalue, 0,
+                               hx + a, hy + a, hv + a, changed.data() + a, ns))
+      return -1;
+    long filled = 0;
+    for (int k = a; k < a + ns; ++k) {
+      if (!changed[k]) continue;
+      if (r.changed) r.changed[k] |= 1;
+      ++written;
+      filled += hv[k] >= 0;
+    }
+    if (r.runs) ++r.runs[s];
+    if (r.filled) r.filled[s] += filled;
+  }
+  if (!written) return 0;
+  if (move_lists(c, q, hx, hipMemcpyHostToDevice, st)) return -1;
+  if (q.tab_x) {  // the row carries every list after the replacement
+    const size_t nb = sizeof(float) * (size_t)n;
+    HIPCHK(c, hipMemcpyAsync(q.tab_x + row * q.tab_stride, q.x, nb, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(q.tab_y + row * q.tab_stride, q.y, nb, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(q.tab_val + row * q.tab_stride, q.val, nb, hipMemcpyDeviceToDevice, st));
+  }
+  return 0;
+}
+
+// both calls; rep == nullptr: klt_hip_track_frames_multi
+int track_multi(klt_hip_ctx *c, const char *who, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td,
+                const MultiReplace *rep, const unsigned char *frames, long pitch, long stride, long seq_stride, int nseq,
+                int nframes, int chunk, const int *n_seq, float *x, float *y, int *val, float *tab_x, float *tab_y,
+                int *tab_val, long tab_stride) {
   if (!c || !pd || !td || !n_seq) return fail(c, "%s: null argument", who);
-  if (c->rep_on) return fail(c, "%s: not covered while lost features are replaced (klt_hip_set_frames_replace)", who);
+  if (rep && !rep->d) return fail(c, "%s: null replacement description", who);
+  if (c->rep_on)
+    return rep ? fail(c, "%s: the context's own replacement setting is on; it belongs to the single-sequence calls "
+                      "(klt_hip_set_frames_replace)", who)
+               : fail(c, "%s: not covered while lost features are replaced (klt_hip_set_frames_replace)", who);
+  if (rep && replace_desc_refused(c, rep->d, who)) return -1;
+  if (rep && rep->count0 < 0) return fail(c, "%s: count0 %ld < 0", who, rep->count0);
   if (nseq < 1 || nseq > KLT_HIP_MAX_SEQUENCES)
     return fail(c, "%s: nseq %d is not in 1..%d", who, nseq, KLT_HIP_MAX_SEQUENCES);
   if (nframes < 0 || chunk < 1) return fail(c, "%s: bad nframes/chunk", who);
@@ -69,7 +191,7 @@ KLT_API int klt_hip_track_frames_multi(klt_hip_ctx *c, const klt_hip_pyr_desc *p
   if (ntab && tab_stride < n) return fail(c, "%s: table stride %ld < n %d", who, tab_stride, n);
   if (pitch < (long)pd->ncols * frame_bpp(c->frame_format))
     return fail(c, "%s: pitch %ld < ncols %d * %d bytes per pixel", who, pitch, pd->ncols, frame_bpp(c->frame_format));
-  if (multi_refused(c, pd, td)) return -1;
+  if (multi_refused(c, pd, td, who)) return -1;
   if (nframes == 0) return 0;
   if (use_device(c)) return -1;
 
@@ -101,47 +223,128 @@ KLT_API int klt_hip_track_frames_multi(klt_hip_ctx *c, const klt_hip_pyr_desc *p
   a.aos = 1;
   hipStream_t st = c->stream;
   const bool frame_major = stride == (long)nseq * seq_stride;
+  const MultiCall q{pd, nseq, n, &ms, x, y, val, tab_x, tab_y, tab_val, tab_stride};
+
+  // a chunk's pyramids: F frames of every sequence from call frame j0 + 1 into bank K
+  const auto build = [&](Bank &K, int j0, int F) -> int {
+    const unsigned char *src = frames + (long)(j0 + 1) * stride;
+    if (frame_major)
+      return build_fused_bank(c, K, pd, src, pitch, seq_stride, nseq * F, st, 0, 1 << 30, 0, 1 << 30, kLayoutRec);
+    for (int s = 0; s < nseq; ++s)
+      if (build_fused_bank(c, K, pd, src + (long)s * seq_stride, pitch, stride, F, st, 0, 1 << 30, 0, 1 << 30,
+                           kLayoutRec, s, nseq))
+        return -1;
+    return 0;
+  };
 
   // the start images' group: pyramids 0 .. nseq-1 of a bank
   int bi = c->bank_next;
   if (build_fused_bank(c, c->bank[bi], pd, frames, pitch, seq_stride, nseq, st, 0, 1 << 30, 0, 1 << 30, kLayoutRec))
     return -1;
   long prev_first = 0;  // the group this chunk starts from: pyramids prev_first .. +nseq of bank bi
+  bool built = false;   // this chunk's pyramids were queued at the previous chunk's last cut
   for (int j0 = 0; j0 < nframes; j0 += F0) {
     const int F = F0 < nframes - j0 ? F0 : nframes - j0, pb = bi;
     bi = (bi + 1) % 3;
     Bank &K = c->bank[bi];
-    const unsigned char *src = frames + (long)(j0 + 1) * stride;
-    if (frame_major) {
-      if (build_fused_bank(c, K, pd, src, pitch, seq_stride, nseq * F, st, 0, 1 << 30, 0, 1 << 30, kLayoutRec))
-        return -1;
-    } else {
-      for (int s = 0; s < nseq; ++s)
-        if (build_fused_bank(c, K, pd, src + (long)s * seq_stride, pitch, stride, F, st, 0, 1 << 30, 0, 1 << 30,
-                             kLayoutRec, s, nseq))
-          return -1;
-    }
-    TrkFramesArgs b;
-    memset(&b, 0, sizeof b);
-    for (int l = 0; l < pd->nlevels; ++l) {
-      a.A[l] = level_view(c->bank[pb].lv[l], prev_first);
-      a.B[l] = level_view(K.lv[l], 0);
-      b.lfs[l] = (long)K.lv[l].w * K.lv[l].h * 3;
-    }
-    b.nframes = F;
-    if (tab_x) {
-      b.tx = tab_x + (long)j0 * tab_stride;
-      b.ty = tab_y + (long)j0 * tab_stride;
-      b.tv = tab_val + (long)j0 * tab_stride;
-      b.tstride = tab_stride;
-    }
-    b.count = c->d_trk_count;
-    if (n > 0) {
-      TimedScope ts(c, T_TRACK, st, F);
-      if (launched(c, "k_track7_multi", launch_track7_multi(st, a, b, ms, x, y, val, n, &c->track_kernel))) return -1;
+    if (!built && build(K, j0, F)) return -1;
+    built = false;
+    const int jn = j0 + F, Fn = F0 < nframes - jn ? F0 : nframes - jn;
+    for (int f0 = 0; f0 < F;) {
+      // up to the next frame at which a replacement is due
+      int f1 = F;
+      if (rep) {
+        const long due = rep->d->every - (rep->count0 + j0 + f0) % rep->d->every;
+        if (f0 + due < F) f1 = (int)(f0 + due);
+      }
+      TrkFramesArgs b;
+      memset(&b, 0, sizeof b);
+      for (int l = 0; l < pd->nlevels; ++l) {
+        a.A[l] = f0 ? level_view(K.lv[l], (long)(f0 - 1) * nseq) : level_view(c->bank[pb].lv[l], prev_first);
+        a.B[l] = level_view(K.lv[l], (long)f0 * nseq);
+        b.lfs[l] = (long)K.lv[l].w * K.lv[l].h * 3;
+      }
+      b.nframes = f1 - f0;
+      if (tab_x) {
+        b.tx = tab_x + (long)(j0 + f0) * tab_stride;
+        b.ty = tab_y + (long)(j0 + f0) * tab_stride;
+        b.tv = tab_val + (long)(j0 + f0) * tab_stride;
+        b.tstride = tab_stride;
+      }
+      b.count = c->d_trk_count;
+      if (n > 0) {
+        TimedScope ts(c, T_TRACK, st, f1 - f0);
+        if (launched(c, "k_track7_multi", launch_track7_multi(st, a, b, ms, x, y, val, n, &c->track_kernel))) return -1;
+      }
+      if (rep && (rep->count0 + j0 + f1) % rep->d->every == 0) {
+        const auto ahead = [&]() -> int {
+          if (f1 < F || Fn <= 0) return 0;
+          built = true;
+          return build(c->bank[(bi + 1) % 3], jn, Fn);
+        };
+        if (replace_lost_multi(c, q, *rep, K, f1 - 1, j0 + f1 - 1, ahead)) return -1;
+      }
+      f0 = f1;
     }
     prev_first = (long)(F - 1) * nseq;
   }
   c->bank_next = (bi + 1) % 3;
+  return 0;
+}
+}  // namespace
+
+KLT_API int klt_hip_multi_covers(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td) {
+  if (!c || !pd || !td) return fail(c, "multi_covers: null argument");
+  return multi_refused(c, pd, td, "track_frames_multi") ? 0 : 1;
+}
+
+KLT_API int klt_hip_track_frames_multi(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td,
+                                       const unsigned char *frames, long pitch, long stride, long seq_stride,
+                                       int nseq, int nframes, int chunk, const int *n_seq, float *x, float *y,
+                                       int *val, float *tab_x, float *tab_y, int *tab_val, long tab_stride) {
+  return track_multi(c, "track_frames_multi", pd, td, nullptr, frames, pitch, stride, seq_stride, nseq, nframes, chunk,
+                     n_seq, x, y, val, tab_x, tab_y, tab_val, tab_stride);
+}
+
+KLT_API int klt_hip_track_frames_multi_replace(klt_hip_ctx *c, const klt_hip_pyr_desc *pd,
+                                               const klt_hip_track_desc *td, const klt_hip_replace_desc *rep,
+                                               long count0, const unsigned char *frames, long pitch, long stride,
+                                               long seq_stride, int nseq, int nframes, int chunk, const int *n_seq,
+                                               float *x, float *y, int *val, float *tab_x, float *tab_y, int *tab_val,
+                                               long tab_stride, unsigned char *changed, long *runs, long *filled) {
+  const MultiReplace r{rep, count0, changed, runs, filled};
+  return track_multi(c, "track_frames_multi_replace", pd, td, &r, frames, pitch, stride, seq_stride, nseq, nframes,
+                     chunk, n_seq, x, y, val, tab_x, tab_y, tab_val, tab_stride);
+}
+
+KLT_API int klt_hip_min_eigen_records(klt_hip_ctx *c, const float *dev_rec, long frame_stride, const int *which,
+                                      int nsel, int ncols, int nrows, const klt_hip_select_desc *d, int *dev_maps) {
+  if (!c || !dev_rec || !which || !d || !dev_maps || ncols < 1 || nrows < 1)
+    return fail(c, "min_eigen_records: bad argument");
+  if (nsel < 1 || nsel > kMaxSeq) return fail(c, "min_eigen_records: nsel %d is not in 1..%d", nsel, kMaxSeq);
+  const int step = d->nSkippedPixels + 1;
+  if (d->window_width != 2 * kRG + 1 || d->window_height != 2 * kRG + 1)
+    return fail(c, "min_eigen_records: window %dx%d, the kernel covers 7x7 only", d->window_width, d->window_height);
+  if (step < 1 || step > 2) return fail(c, "min_eigen_records: step %d, the kernel covers 1 and 2", step);
+  if (d->borderx < kRG || d->bordery < kRG) return fail(c, "min_eigen_records: border smaller than window half size");
+  if (frame_stride < (long)ncols * nrows * kRec) return fail(c, "min_eigen_records: frame stride %ld too small", frame_stride);
+  EigMultiArgs m;
+  memset(&m, 0, sizeof m);
+  m.nsel = nsel;
+  for (int i = 0; i < nsel; ++i) {
+    if (which[i] < 0) return fail(c, "min_eigen_records: frame index %d", which[i]);
+    m.seq[i] = which[i];
+  }
+  const int cx = ncols - 2 * d->borderx, cy = nrows - 2 * d->bordery;
+  const int nx = cx > 0 ? (cx + step - 1) / step : 0, ny = cy > 0 ? (cy + step - 1) / step : 0;
+  if ((long)nx * ny == 0) return 0;
+  if (use_device(c)) return -1;
+  {
+    TimedScope ts(c, T_EIG, c->stream);
+    if (launched(c, "k_min_eigen7_multi", launch_min_eigen_multi(c->stream, dev_rec, frame_stride, m, ncols, d->borderx,
+                                                                 d->bordery, step, nx, ny, dev_maps, &c->eig_kernel)))
+      return -1;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -160,6 +160,13 @@ DEVICE_PROTOS = {
     "klt_hip_track_frames_multi": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc), V, C.c_long, C.c_long,
                                              C.c_long, C.c_int, C.c_int, C.c_int, IP, V, V, V, V, V, V, C.c_long]),
     "klt_hip_multi_covers": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc)]),
+    # rep, count0, then klt_hip_track_frames_multi's, then host changed (n bytes), runs and filled (long[nseq])
+    "klt_hip_track_frames_multi_replace": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc),
+                                                     C.POINTER(ReplaceDesc), C.c_long, V, C.c_long, C.c_long,
+                                                     C.c_long, C.c_int, C.c_int, C.c_int, IP, V, V, V, V, V, V,
+                                                     C.c_long, V, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    # dev_rec, frame_stride (floats), which (host int[nsel]), nsel, ncols, nrows, desc, dev_maps
+    "klt_hip_min_eigen_records": (C.c_int, [V, V, C.c_long, IP, C.c_int, C.c_int, C.c_int, C.POINTER(SelectDesc), V]),
     # frames: const unsigned char *const *; rows: klt_hip_rows_fn or NULL
     "klt_hip_track_frames_host": (C.c_int, [V, C.POINTER(PyrDesc), C.POINTER(TrackDesc), V, C.c_int, C.c_int,
                                             C.c_int, V, V, V, C.c_int, V, V]),
