@@ -115,19 +115,20 @@ class KltStepper:
         self.lib.KLTFreeTrackingContext(self.tb)
 
 
-def fb_compose(st, frames, n, nframes, max_dist, first=None, replace=False, stats=None):
+def fb_compose(st, frames, n, nframes, max_dist, first=None, replace=False, stats=None, start=None):
     """KLTRunner.harness's loop with the FB step after every track: X, Y, V
     ([n, nframes], column i-1 = the list after tracking frames[i], column 0
     overwritten like the harness does, the last never written) and E
     ([nframes-1, n], row i-1 = frame i's squared return distances).  stats (a
     dict): "rejected" receives the number of verdicts that rejected a feature
-    (with replacement the table no longer shows them)."""
+    (with replacement the table no longer shows them).  start: the list to
+    track instead of a selection on the first image."""
     img1 = np.ascontiguousarray(frames[1] if first is None else first)
     X = np.zeros((n, nframes), np.float32)
     Y = np.zeros((n, nframes), np.float32)
     V = np.zeros((n, nframes), np.int32)
     E = np.full((nframes - 1, n), -1.0, np.float32)
-    x, y, v = st.select(img1, n)
+    x, y, v = st.select(img1, n) if start is None else tuple(a.copy() for a in start)
     X[:, 0], Y[:, 0], V[:, 0] = x, y, v
     nrej = 0
     for i in range(1, nframes):

@@ -19,11 +19,11 @@ pytestmark = pytest.mark.gpu
 _WANT: dict = {}
 
 
-def want(oracle, key, frames, n, max_dist, params=None, replace=False, nframes=None):
+def want(oracle, key, frames, n, max_dist, params=None, replace=False, nframes=None, start=None):
     if key not in _WANT:
         st = {}
         r = fb_compose(OracleStepper(oracle, params), frames, n, nframes or len(frames), max_dist, first=frames[0],
-                       replace=replace, stats=st)
+                       replace=replace, stats=st, start=start)
         for a in r:
             a.setflags(write=False)
         _WANT[key] = r + (st["rejected"],)
@@ -118,7 +118,7 @@ def test_single_calls(gpu, oracle, frames, max_dist, sequential):
 # ---------------------------------------------------------------------------
 # 2.-4. the batched path (klt_hip_track_frames)
 # ---------------------------------------------------------------------------
-def batch_fb(gpu, frames, nfeat, chunks, max_dist, calls=None, setup=None, hooks=None):
+def batch_fb(gpu, frames, nfeat, chunks, max_dist, calls=None, setup=None, hooks=None, start=None):
     """test_gpu_track.batch_sequence with FB on and the error table pointed at
     each call's first row; hooks: tuning setters applied to the context.
     Returns X, Y, V ([T, n]) and E ([T, n])."""
@@ -142,7 +142,7 @@ def batch_fb(gpu, frames, nfeat, chunks, max_dist, calls=None, setup=None, hooks
 
     gpu.klt_hip_track_frames = call
     try:
-        X, Y, V = batch_sequence(gpu, frames, nfeat, chunks, setup, calls=calls, ctx_hook=hook)
+        X, Y, V = batch_sequence(gpu, frames, nfeat, chunks, setup, calls=calls, ctx_hook=hook, start=start)
     finally:
         gpu.klt_hip_track_frames = orig
     return X, Y, V, state["E"]

@@ -58,11 +58,13 @@ def start_of(gpu, seed, n):
 class Dev:
     """A tracking context's device context with the default descriptors."""
 
-    def __init__(self, gpu, budget=None, search_range=None):
+    def __init__(self, gpu, budget=None, search_range=None, setup=None):
         from kltamd.device import PyrDesc, TrackDesc
         self.gpu = gpu
         self.tc = gpu.KLTCreateTrackingContext()
         self.tc.contents.sequentialMode = 1
+        if setup:  # other fields of the tracking context record, before the descriptors are taken from it
+            setup(self.tc.contents)
         if search_range is not None:
             gpu.KLTChangeTCPyramid(self.tc, search_range)
             gpu.KLTUpdateTCBorder(self.tc)
@@ -107,17 +109,24 @@ class Dev:
             self.gpu.klt_hip_free(self.ctx, d)
         self.gpu.KLTFreeTrackingContext(self.tc)
 
-    def single(self, frames, start, chunk=CHUNK):
+    def single(self, frames, start, chunk=CHUNK, calls=None):
         """klt_hip_frames_begin on frames[0], one klt_hip_track_frames call over
-        the rest: the table [T, n] and the final list."""
+        the rest (or one per entry of `calls`, that many frames each): the table
+        [T, n] and the final list."""
         x, y, v = start
         n = len(x)
         dfr = self.up(np.stack(frames))
         dx, dy, dv = self.up(x), self.up(y), self.up(v)
         tx, ty, tv = (self.up(np.zeros(T * max(n, 1), F32)) for _ in range(3))
         self.ok(self.gpu.klt_hip_frames_begin(self.ctx, C.byref(self.pd), dfr, W), "begin")
-        self.ok(self.gpu.klt_hip_track_frames(self.ctx, C.byref(self.pd), C.byref(self.td), dfr + W * H, W, W * H, T,
-                                              chunk, dx, dy, dv, n, tx, ty, tv, n), "frames")
+        j = 0
+        for nf in calls or [T]:
+            off = 4 * j * n
+            self.ok(self.gpu.klt_hip_track_frames(self.ctx, C.byref(self.pd), C.byref(self.td), dfr + (j + 1) * W * H,
+                                                  W, W * H, nf, chunk, dx, dy, dv, n, tx + off, ty + off, tv + off,
+                                                  n), "frames")
+            j += nf
+        assert j == T
         return (self.down(tx, (T, n), F32), self.down(ty, (T, n), F32), self.down(tv, (T, n), np.int32),
                 self.down(dx, n, F32), self.down(dy, n, F32), self.down(dv, n, np.int32))
 

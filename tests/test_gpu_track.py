@@ -226,8 +226,8 @@ def test_pipelined_generic_path_vs_oracle(gpu, oracle):
     assert np.array_equal(x.view(np.int32), X[:, 5].view(np.int32)) and np.array_equal(v, V[:, 5])
 
 
-def batch_sequence(gpu, frames, nfeat, chunks, setup=None, calls=None, counts=None, ctx_hook=None):
-    """Select on frames[0], then klt_hip_frames_begin + klt_hip_track_frames over
+def batch_sequence(gpu, frames, nfeat, chunks, setup=None, calls=None, counts=None, ctx_hook=None, start=None):
+    """Select on frames[0] (or take the list `start`), then klt_hip_frames_begin + klt_hip_track_frames over
     frames[1:] (split into `calls` pieces, one chunk size per call), returning
     the device feature table: row j = the list after frame j+1.  counts (a
     list): the tracker's work counters (klt_hip_set_track_count) are appended.
@@ -243,7 +243,7 @@ def batch_sequence(gpu, frames, nfeat, chunks, setup=None, calls=None, counts=No
     ctx = gpu.klt_amd_device_context(tc)
     fl = gpu.KLTCreateFeatureList(nfeat)
     gpu.KLTSelectGoodFeatures(tc, u8ptr(np.ascontiguousarray(frames[0])), w, h, fl)
-    x, y, v = fl_to_arrays(fl)
+    x, y, v = fl_to_arrays(fl) if start is None else tuple(np.array(a) for a in start)
     gpu.KLTFreeFeatureList(fl)
     stack = np.ascontiguousarray(np.stack(frames))
     T = len(frames) - 1
