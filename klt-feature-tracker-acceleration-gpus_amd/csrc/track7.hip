@@ -175,7 +175,12 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // NS ordered sums: lane p (< 49) contributes v[s] as pixel p of sum s; returns
 // the sums, wave-uniform.  The reference's sequential float sums (:241-248,
 // :271-278, :354-367), each from +0 in pixel order.
-template <int NS>
+// PIN (the lazy-gradient instances, which run at their scalar register limit):
+// the test lane < NS is made anew from a lane number the compiler cannot see
+// through, one compare.  Left to itself it keeps the three masks (NS 1, 5, 6)
+// as frame-loop invariants in scalar pairs, spills them and reads them back
+// lane by lane in every pass.
+template <int NS, bool PIN = false>
 __device__ __forceinline__ void sums7(float *red, int lane, bool on, const float (&v)[NS], float (&out)[NS]) {
   if (on) {
 #pragma unroll
@@ -183,6 +188,7 @@ __device__ __forceinline__ void sums7(float *red, int lane, bool on, const float
   }
   wave_lds_sync();
   float acc = 0.0f;
+  if constexpr (PIN) asm volatile("" : "+v"(lane));
   if (lane < NS) {
     const float *r = red + lane * kRow;
     constexpr int NCH = kRow / 4, B = KLT_T7_BATCH;
@@ -261,10 +267,10 @@ __device__ __forceinline__ void tree7(bool on, const float (&v)[NS], float (&out
 #endif
 }
 
-template <int NS, bool FAST>
+template <int NS, bool FAST, bool PIN = false>
 __device__ __forceinline__ void sums(float *red, int lane, bool on, const float (&v)[NS], float (&out)[NS]) {
   if constexpr (FAST) tree7<NS>(on, v, out);
-  else sums7<NS>(red, lane, on, v, out);
+  else sums7<NS, PIN>(red, lane, on, v, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -329,7 +335,13 @@ __device__ __forceinline__ void patch_grads(float *pat, int lane, const TrkArgs 
     qi.r0 = make_float2(S[0], S[1]);
     qi.r1 = make_float2(S[kPS], S[kPS + 1]);
   }
-  // rows pass: {tx, ty} of block rows r and r + 8 (rows 14 and 15 are spare), column c = pixel X0 + c
+  // rows pass: {tx, ty} of block rows r and r + 8 (rows 14 and 15 are spare), column c = pixel X0 + c.
+  // Both passes multiply by the same seven scalar pairs {gd[m], gg[m]}: tx takes
+  // gd here and gg in the columns pass, ty the other way round, so T holds each
+  // pair exchanged, {ty, tx} (two 4-byte stores from either register, one LDS
+  // instruction), and the columns pass forms {gy, gx}.  With {gg[m], gd[m]} for
+  // the columns as well, the packed multiplies' aligned scalar pairs took 28
+  // registers, most of them spilled and read back lane by lane in every patch.
   const int c = lane & 7, r = lane >> 3;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
@@ -337,17 +349,19 @@ __device__ __forceinline__ void patch_grads(float *pat, int lane, const TrkArgs 
     f2 t = {0.0f, 0.0f};
 #pragma unroll
     for (int m = 0; m < 7; ++m) t += f2{row[m], row[m]} * f2{a.gd[m], a.gg[m]};
-    *reinterpret_cast<f2 *>(pat + kPatS + 2 * ((r + 8 * k) * 8 + c)) = t;
+    float *T = pat + kPatS + 2 * ((r + 8 * k) * 8 + c);
+    T[0] = t.y;
+    T[1] = t.x;
   }
   wave_lds_sync();
-  // columns pass: {gx, gy} of pixel (X0 + c, Y0 + r) from T rows r .. r + 6; G goes over S
+  // columns pass: {gy, gx} of pixel (X0 + c, Y0 + r) from T rows r .. r + 6; G goes over S
   {
     const float *col = pat + kPatS + 2 * (r * 8 + c);
     f2 g = {0.0f, 0.0f};
 #pragma unroll
-    for (int m = 0; m < 7; ++m) g += *reinterpret_cast<const f2 *>(col + 16 * m) * f2{a.gg[m], a.gd[m]};
+    for (int m = 0; m < 7; ++m) g += *reinterpret_cast<const f2 *>(col + 16 * m) * f2{a.gd[m], a.gg[m]};
     const int x = X0 + c, y = Y0 + r;
-    if (x < kHw || x >= w - kHw || y < kHw || y >= h - kHw) g = f2{0.0f, 0.0f};
+    if (x < kHw || x + kHw >= w || y < kHw || y + kHw >= h) g = f2{0.0f, 0.0f};  // w and h as they are: no w - 3, h - 3 to keep
     *reinterpret_cast<f2 *>(pat + 2 * (r * 8 + c)) = g;
   }
   wave_lds_sync();
@@ -356,10 +370,10 @@ __device__ __forceinline__ void patch_grads(float *pat, int lane, const TrkArgs 
   const f2 g01 = *reinterpret_cast<const f2 *>(pat + 2 * (cy * 8 + cx1));
   const f2 g10 = *reinterpret_cast<const f2 *>(pat + 2 * (cy1 * 8 + cx));
   const f2 g11 = *reinterpret_cast<const f2 *>(pat + 2 * (cy1 * 8 + cx1));
-  qx.r0 = make_float2(g00.x, g01.x);
-  qx.r1 = make_float2(g10.x, g11.x);
-  qy.r0 = make_float2(g00.y, g01.y);
-  qy.r1 = make_float2(g10.y, g11.y);
+  qx.r0 = make_float2(g00.y, g01.y);
+  qx.r1 = make_float2(g10.y, g11.y);
+  qy.r0 = make_float2(g00.x, g01.x);
+  qy.r1 = make_float2(g10.x, g11.x);
   wave_lds_sync();  // the patch area is rewritten by the next patch
 }
 
@@ -423,6 +437,20 @@ __device__ __forceinline__ Lev lev_before(const TrkArgs &a, const TrkFramesArgs 
   }
 }
 
+// ROLL (track7_body.h): image 1's base and level-0 layout come with the
+// caller, the level's size is image 2's (launch_track7 refuses a kept pyramid
+// of another size)
+template <bool MULTI, bool ROLL>
+__device__ __forceinline__ Lev lev_img1(const TrkArgs &a, const TrkFramesArgs &b, int r, int j, int sq, int nsq,
+                                        const float *pimg, int pil) {
+  if constexpr (ROLL) {
+    const TrkLevel &Q = a.B[r];
+    return Lev{pimg, nullptr, nullptr, Q.w, Q.h, Q.vlo, Q.vhi, a.oobx[r], a.ooby[r], pil};
+  } else {
+    return lev_before<MULTI>(a, b, r, j, sq, nsq);
+  }
+}
+
 // band-built pyramids (klt_hip_track_frames_band): every row the window's
 // bilinear samples touch must have been built
 __device__ __forceinline__ bool band_bad(const Lev &L, float y) {
@@ -467,12 +495,34 @@ __device__ __forceinline__ void wave_time(unsigned long long *wave_t, int which,
   const unsigned long long xcd = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20) & 15u;
   if (k < cap) wave_t[4 + which * cap + k] = (t & kWaveTimeMask) | (xcd << kWaveXcdShift);
 }
-__device__ __forceinline__ void wave_exit(const TrkFramesArgs &b, int lane, unsigned k) {
+// What a wave needs only as it leaves -- the list's pointers, the work
+// counters, the hook's -- the lazy-gradient instances read from the kernel's
+// argument segment there (track7_body.h's LATE) and not from the by-value
+// arguments, which are loaded at the kernel's entry and would be held in scalar
+// registers, or spilled and reloaded, all through the frame loop.  T7KArgs is
+// the explicit arguments of k_track7 / k_track7_hook as the segment holds them:
+// in order, each at its natural alignment.
+struct T7KArgs {
+  TrkArgs a;
+  TrkFramesArgs b;
+  float *fx, *fy;
+  int *fv;
+  int n;
+};
+typedef const __attribute__((address_space(4))) T7KArgs *T7KArgsPtr;
+__device__ __forceinline__ T7KArgsPtr t7_kargs() {
+  return (T7KArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+}
+// the hook's way out (the HOOK instances are lazy-gradient ones)
+__device__ __forceinline__ void wave_exit(int lane, unsigned k) {
   if (lane != 0) return;
-  if (b.wave_t) wave_time(b.wave_t, 1, k);
-  if (b.exits) {
-    const unsigned k = atomicAdd(b.exits, 1u) + 1u;
-    if (k == b.exit_thr) __hip_atomic_store(b.exit_sig, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  const T7KArgsPtr ka = t7_kargs();
+  unsigned long long *const wave_t = ka->b.wave_t;
+  unsigned *const exits = ka->b.exits;
+  if (wave_t) wave_time(wave_t, 1, k);
+  if (exits) {
+    const unsigned k = atomicAdd(exits, 1u) + 1u;
+    if (k == ka->b.exit_thr) __hip_atomic_store(ka->b.exit_sig, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -528,7 +578,7 @@ __device__ __forceinline__ int pass7(const TrkArgs &a, const Lev &A, const Lev &
           interp(q, AOS && !LZ ? quad_i(R.img, q, (unsigned)R.w * 12u) : quad(R.img, q, (unsigned)R.w * 4u));
       float v[1] = {on ? fabsf(pd.aim - rb) : 0.0f}, S[1];
       ++cnt.passes;
-      sums<1, FAST>(red, lane, on, v, S);
+      sums<1, FAST, LZ != 0>(red, lane, on, v, S);
       rstat = S[0] / (float)kNpx > a.max_res ? kLargeResidue : (pd.it >= a.max_it ? kMaxIter : kTracked);
       pd.on = false;
       if (rstat != kTracked) return kPassLostPrev;
@@ -637,14 +687,14 @@ __device__ __forceinline__ int pass7(const TrkArgs &a, const Lev &A, const Lev &
   if (JOB) {
     const float rb = interp(qr, ri);
     float v[6] = {gxs * gxs, gxs * gys, gys * gys, dif * gxs, dif * gys, fabsf(pd.aim - rb)};
-    sums<6, FAST>(red, lane, on, v, S);
+    sums<6, FAST, LZ != 0>(red, lane, on, v, S);
     rstat = S[5] / (float)kNpx > a.max_res ? kLargeResidue : (pd.it >= a.max_it ? kMaxIter : kTracked);
     pd.on = false;
     if (rstat != kTracked) return kPassLostPrev;  // that frame's feature is lost: this frame does not happen
   } else {
     float v[5] = {gxs * gxs, gxs * gys, gys * gys, dif * gxs, dif * gys};
     float S5[5];
-    sums<5, FAST>(red, lane, on, v, S5);
+    sums<5, FAST, LZ != 0>(red, lane, on, v, S5);
 #pragma unroll
     for (int k = 0; k < 5; ++k) S[k] = S5[k];
   }
@@ -726,7 +776,7 @@ __device__ int level7(const TrkArgs &a, const Lev &A, const Lev &B, float x1, fl
   const float rb =
       interp(q, AOS && LZ != 2 ? quad_i(B.img, q, (unsigned)B.w * 12u) : quad(B.img, q, (unsigned)B.w * 4u));
   float v[1] = {on ? fabsf(ls.aim - rb) : 0.0f}, S1[1];
-  sums<1, FAST>(red, lane, on, v, S1);
+  sums<1, FAST, LZ != 0>(red, lane, on, v, S1);
   T7_ADD(3, t_r0);
   if (S1[0] / (float)kNpx > a.max_res) return kLargeResidue;
   return ls.it >= a.max_it ? kMaxIter : kTracked;
@@ -882,6 +932,11 @@ hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const T
   }
   if (a.lazy) {  // the runtime sends whole-frame interleaved pyramids here (fast sums: two levels)
     if (band || !a.aos || (a.fast && !two)) return hipErrorInvalidValue;
+    // the bank's level 0 is an img plane, and the kept pyramid has the bank's
+    // level sizes: the kernels take image 1's from image 2's (lev_img1)
+    if (a.B[0].il != kLayoutImg) return hipErrorInvalidValue;
+    for (int l = 0; l < a.nlev; ++l)
+      if (a.A[l].w != a.B[l].w || a.A[l].h != a.B[l].h) return hipErrorInvalidValue;
     if (name)
       *name = a.fast ? "kltdev::k_track7<false, true, 2, true, true>"
               : two  ? "kltdev::k_track7<false, true, 2, false, true>"

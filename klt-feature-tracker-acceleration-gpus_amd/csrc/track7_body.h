@@ -4,7 +4,15 @@
 // instances existed.  The including kernel provides: the template parameters
 // BAND, AOS, NL, FAST, LAZY, HOOK; constexpr bool FB, MULTI; TrkArgs a;
 // TrkFramesArgs b; TrkFbArgs fb; TrkMultiArgs ms; fx, fy, fv, n; and the LDS
-// array red_all.
+// array red_all.  The lazy-gradient instances run at their scalar register
+// limit; what LATE, ROLL and the pinned lane numbers below do for them keeps
+// spilled scalars and argument loads out of their frame loop (DESIGN section 4,
+// "Scalar spills off the lazy tracker's chain").  Every other instance
+// compiles to the code it was.
+  // LATE: what only a leaving wave needs is read from the argument segment
+  // there (track7.hip's T7KArgs: the arguments of k_track7 / k_track7_hook)
+  constexpr bool LATE = LAZY && !FB && !MULTI;
+  static_assert(!HOOK || LATE, "wave_exit reads T7KArgs");
   if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   if constexpr (HOOK)
@@ -13,13 +21,13 @@
   // XCD-major block order over the (band-sorted) features actually processed
   const int xcd_per = b.n_dev && b.xcd_per > 0 ? ((n + kWaves - 1) / kWaves + 7) / 8 : b.xcd_per;
   if (xcd_per > 0 && (int)(blockIdx.x / 8) >= xcd_per) {
-    if constexpr (HOOK) wave_exit(b, lane, blockIdx.x * kWaves + wave);
+    if constexpr (HOOK) wave_exit(lane, blockIdx.x * kWaves + wave);
     return;
   }
   const int blk = xcd_per > 0 ? (int)(blockIdx.x % 8) * xcd_per + (int)(blockIdx.x / 8) : (int)blockIdx.x;
   const int slot = blk * kWaves + wave;
   if (slot >= n) {  // whole wave; no workgroup barrier in this kernel
-    if constexpr (HOOK) wave_exit(b, lane, slot);
+    if constexpr (HOOK) wave_exit(lane, slot);
     return;
   }
   const int f = u(b.perm ? b.perm[slot] : slot);
@@ -57,6 +65,18 @@
 #ifdef KLT_TRACK_PROF
   const unsigned long long wall0 = wall_clock64();
 #endif
+  // ROLL (the lazy-gradient instances of a compile-time depth): image 1's level
+  // bases are carried from frame to frame -- the kept pyramid's (a.A) for the
+  // launch's first frame, then the bank frame just tracked -- with its level-0
+  // layout, so that the frame loop selects nothing and reads no field of a.A
+  constexpr bool ROLL = LAZY && NL > 0 && !FB && !MULTI;
+  const float *pimg[NL > 0 ? NL : 1] = {};
+  int pil = kLayoutImg;
+  if constexpr (ROLL) {
+#pragma unroll
+    for (int r = 0; r < NL; ++r) pimg[r] = a.A[r].img;
+    pil = a.A[0].il;
+  }
   for (int j = 0; j < b.nframes; ++j) {
     T7_T(t_f0);
     const bool job = pd.on;  // frame j-1 is tentatively tracked at (x, y)
@@ -64,7 +84,7 @@
     int rstat = kTracked;
     if (v >= 0 || job) {
       // one frame of KLTTrackFeatures for this feature (:1348-1437)
-      const Lev R = lev_before<MULTI>(a, b, 0, j, sq, nsq);
+      const Lev R = lev_img1<MULTI, ROLL>(a, b, 0, j, sq, nsq, pimg[0], pil);
       // the corners kept from frame j-1 serve this frame's level 0 only: a frame
       // that does not reach level 0 leaves nothing for the one after it
       const unsigned cpx = carry.px;
@@ -84,7 +104,7 @@
         yl = u(yl * a.ss);
         xo = u(xo * a.ss);
         yo = u(yo * a.ss);
-        const Lev LA = lev_before<MULTI>(a, b, r, j, sq, nsq);
+        const Lev LA = lev_img1<MULTI, ROLL>(a, b, r, j, sq, nsq, pimg[ROLL ? r : 0], pil);
         const Lev LB = lev_cur<MULTI>(a, b, r, j, sq, nsq);
         const bool lj = job && r == nlev - 1;
         T7_T(t_l0);
@@ -161,22 +181,31 @@
       }
       if (fb.err && lane == 0) fb.err[j * fb.stride + f] = e;
     }
+    // the table's writer: in the LATE instances a lane number the compiler cannot
+    // see through, so that it keeps no lane mask alive (or spilled) over the frames
+    int tl = lane;
+    if constexpr (LATE) asm volatile("" : "+v"(tl));
     if (job) {  // frame j-1's verdict came with frame j's first pass
       if (rstat != kTracked) {
         x = -1.0f;
         y = -1.0f;
         v = rstat;
       }
-      if (b.tx && lane == 0) {
+      if (b.tx && tl == 0) {
         b.tx[(j - 1) * b.tstride + f] = rstat != kTracked ? -1.0f : xp;
         b.ty[(j - 1) * b.tstride + f] = rstat != kTracked ? -1.0f : yp;
         b.tv[(j - 1) * b.tstride + f] = rstat;
       }
     }
-    if (b.tx && lane == 0 && !pd.on) {
+    if (b.tx && tl == 0 && !pd.on) {
       b.tx[j * b.tstride + f] = x;
       b.ty[j * b.tstride + f] = y;
       b.tv[j * b.tstride + f] = v;
+    }
+    if constexpr (ROLL) {  // this frame's image 2 is the next frame's image 1
+#pragma unroll
+      for (int r = 0; r < NL; ++r) pimg[r] = a.B[r].img + (long)j * b.lfs[r];
+      pil = kLayoutImg;
     }
     T7_ADD(4, t_f0);
   }
@@ -190,13 +219,22 @@
     for (int k = 0; k < kProfN; ++k) b.prof[(long)slot * kProfN + k] = cnt.c[k];
 #endif
   if (lane == 0) {
-    fx[f] = x;
-    fy[f] = y;
-    fv[f] = v;
-    if (b.count) {
+    float *ox = fx, *oy = fy;
+    int *ov = fv;
+    unsigned long long *count = nullptr;
+    if constexpr (LATE) {
+      const T7KArgsPtr ka = t7_kargs();
+      ox = ka->fx, oy = ka->fy, ov = ka->fv, count = ka->b.count;
+    } else {
+      count = b.count;
+    }
+    ox[f] = x;
+    oy[f] = y;
+    ov[f] = v;
+    if (count) {
       const int k = slot & (kCountSlots - 1);
-      atomicAdd(&b.count[k], (unsigned long long)cnt.solves);
-      atomicAdd(&b.count[kCountSlots + k], (unsigned long long)cnt.passes);
+      atomicAdd(&count[k], (unsigned long long)cnt.solves);
+      atomicAdd(&count[kCountSlots + k], (unsigned long long)cnt.passes);
     }
   }
-  if constexpr (HOOK) wave_exit(b, lane, f);
+  if constexpr (HOOK) wave_exit(lane, f);
