@@ -820,6 +820,13 @@ int klt_hip_get_timing(klt_hip_ctx *ctx, klt_hip_timing *out);
 /* numerics self-checks used by the tests: f64 sqrt and f32 divide on device */
 int klt_hip_selftest_sqrt(klt_hip_ctx *ctx, const double *in, double *out, int n);
 int klt_hip_selftest_div(klt_hip_ctx *ctx, const float *a, const float *b, float *out, int n);
+/* the default tracker's 2x2 solve, wave-uniform and on two lanes, on the same
+   n cases (host arrays): sums[5 i ..] = {gxx, gxy, gyy, sum(dif gx), sum(dif gy)},
+   step the step factor; out[6 i ..] = {dx, dy} of the uniform solve, of the
+   two-lane solve from the ordered sums' lanes, of the two-lane solve from uniform
+   sums; ok[i] bit k: solve k found det >= min_det (its outputs are 0 otherwise) */
+int klt_hip_selftest_solve2(klt_hip_ctx *ctx, const float *sums, float step, float min_det, float *out, int *ok,
+                            int n);
 /* host-only self-check of the thread pool behind klt_hip_track_frames_host's
    pinned staging: `rounds` back-to-back groups of pieces (sizes and offsets
    varying per round, up to max_bytes) copied by `workers` threads plus the

@@ -326,6 +326,7 @@ hipError_t launch_to_il(hipStream_t st, const float *plane, float *il, int field
 // n 32-bit words, 16-byte aligned ends (device or mapped pinned host memory)
 hipError_t launch_copy_words(hipStream_t st, const void *src, void *dst, long n);
 hipError_t launch_selftest_div(const float *a, const float *b, float *out, int n);
+hipError_t launch_selftest_solve2(const float *in, float step, float min_det, float *out, int *ok, int n);
 
 // the tracker: one wave per feature; patch/win7 select the lane-patch gather
 // and the compiled-in 7x7 window, npx the pixels-per-lane instance

@@ -1358,6 +1358,43 @@ __global__ void k_selftest_div(const float *a, const float *b, float *out, int n
   if (i < n) out[i] = a[i] / b[i];
 }
 
+// The tracker's 2x2 solve both ways on the same sums (track7_solve.h), one wave
+// per case: in[5 i ..] = {gxx, gxy, gyy, sum(dif gx), sum(dif gy)}; out[6 i ..] =
+// {dx, dy} of solve1, of solve2 from the sums in their lanes (every other lane a
+// NaN, as nothing may read it) and of solve2u; ok[i]: bit k set when solve k
+// found det >= min_det (its outputs are 0 otherwise).
+#include "track7_solve.h"
+__global__ __launch_bounds__(kWave) void k_selftest_solve2(const float *in, float step, float min_det, float *out,
+                                                           int *ok, int n) {
+  const int lane = threadIdx.x;
+  for (int i = blockIdx.x; i < n; i += gridDim.x) {
+    float S[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      S[k] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(in[5 * (long)i + k])));
+    const float acc = lane == kSumGxx   ? S[0]
+                      : lane == kSumGxy ? S[1]
+                      : lane == kSumGyy ? S[2]
+                      : lane == kSumEx  ? S[3]
+                      : lane == kSumEy  ? S[4]
+                                        : __int_as_float(0x7fc00000 + lane);
+    float dx = 0.0f, dy = 0.0f, d = 0.0f, du = 0.0f;
+    // det as pass7 forms it for either solve: from the uniform sums, from the lanes
+    const float det1 = solve_det(S[0], S[1], S[2]);
+    const float det2 = solve_det(lane_of(acc, kSumGxx), lane_of(acc, kSumGxy), lane_of(acc, kSumGyy));
+    const int k1 = !(det1 < min_det), k2 = !(det2 < min_det), k3 = k1;
+    if (k1) solve1(S, step, det1, dx, dy);
+    if (k2) d = solve2(acc, lane_of(acc, kSumGxy), step, det2);
+    if (k3) du = solve2u(S, lane == 0, step, det1);
+    const float r[6] = {dx, dy, lane_of(d, 0), lane_of(d, 1), lane_of(du, 0), lane_of(du, 1)};
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) out[6 * (long)i + k] = r[k];
+      ok[i] = k1 | (k2 << 1) | (k3 << 2);
+    }
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1651,6 +1688,12 @@ hipError_t launch_selftest_sqrt(const double *in, double *out, int n) {
 
 hipError_t launch_selftest_div(const float *a, const float *b, float *out, int n) {
   hipLaunchKernelGGL(k_selftest_div, dim3(blocks_for(n)), dim3(kBlock), 0, 0, a, b, out, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_selftest_solve2(const float *in, float step, float min_det, float *out, int *ok, int n) {
+  const int grid = n < 4096 ? (n > 0 ? n : 1) : 4096;
+  hipLaunchKernelGGL(k_selftest_solve2, dim3(grid), dim3(kWave), 0, 0, in, step, min_det, out, ok, n);
   return hipGetLastError();
 }
 

@@ -930,3 +930,21 @@ KLT_API int klt_hip_selftest_div(klt_hip_ctx *c, const float *a, const float *b,
   if (e != hipSuccess) return fail(c, "selftest_div: %s", hipGetErrorString(e));
   return 0;
 }
+
+KLT_API int klt_hip_selftest_solve2(klt_hip_ctx *c, const float *sums, float step, float min_det, float *out, int *ok,
+                                    int n) {
+  if (use_device(c)) return -1;
+  if (n < 0) return fail(c, "selftest_solve2: n < 0");
+  const size_t m = n ? n : 1;
+  float *d = nullptr;
+  HIPCHK(c, hipMalloc((void **)&d, sizeof(float) * 12 * m));  // 5 n sums, 6 n results, n flags
+  float *dout = d + 5 * m;
+  int *dok = reinterpret_cast<int *>(d + 11 * m);
+  hipError_t e = hipMemcpy(d, sums, sizeof(float) * 5 * n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_selftest_solve2(d, step, min_det, dout, dok, n);
+  if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(float) * 6 * n, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ok, dok, sizeof(int) * n, hipMemcpyDeviceToHost);
+  hipFree(d);
+  if (e != hipSuccess) return fail(c, "selftest_solve2: %s", hipGetErrorString(e));
+  return 0;
+}

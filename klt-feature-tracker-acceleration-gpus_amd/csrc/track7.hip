@@ -22,7 +22,10 @@
 //   * the five (or six) ordered sums go through LDS once per pass: each lane
 //     writes its products, lane s reads row s with all thirteen 16-byte reads
 //     in flight and adds them in pixel order -- the reference's sequential
-//     float sum, started from +0 (the rows' pads past pixel 48 stay +0).
+//     float sum, started from +0 (the rows' pads past pixel 48 stay +0);
+//   * the 2x2 solve runs on two lanes (track7_solve.h): the sums stay in the
+//     lanes that added them, lane 0 divides for dx and lane 1 for dy with one
+//     instruction stream, and the position is kept in those two lanes.
 // Parity: -ffp-contract=off, IEEE division, every expression in the
 // reference's evaluation order.
 #pragma clang fp contract(off)
@@ -55,6 +58,8 @@ constexpr int kWaves = kBlock / kWave;
 
 __device__ __forceinline__ float u(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 __device__ __forceinline__ int u(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+#include "track7_solve.h"  // KLT_T7_SOLVE2: the solve on two lanes
 
 // window bounds test (trackFeatures.c:421-427 / :460-462, one_plus_eps 1.001):
 //   x - 3 < 0 || w - (x + 3) < 1.001 || (the same for y and h)
@@ -180,8 +185,9 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // through, one compare.  Left to itself it keeps the three masks (NS 1, 5, 6)
 // as frame-loop invariants in scalar pairs, spills them and reads them back
 // lane by lane in every pass.
+// sums7_acc leaves sum s in lane s (the two-lane solve takes them there).
 template <int NS, bool PIN = false>
-__device__ __forceinline__ void sums7(float *red, int lane, bool on, const float (&v)[NS], float (&out)[NS]) {
+__device__ __forceinline__ float sums7_acc(float *red, int lane, bool on, const float (&v)[NS]) {
   if (on) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) red[s * kRow + lane] = v[s];
@@ -209,9 +215,14 @@ __device__ __forceinline__ void sums7(float *red, int lane, bool on, const float
       }
     }
   }
+  wave_lds_sync();  // the rows are rewritten by the next pass
+  return acc;
+}
+template <int NS, bool PIN = false>
+__device__ __forceinline__ void sums7(float *red, int lane, bool on, const float (&v)[NS], float (&out)[NS]) {
+  const float acc = sums7_acc<NS, PIN>(red, lane, on, v);
 #pragma unroll
   for (int s = 0; s < NS; ++s) out[s] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), s));
-  wave_lds_sync();  // the rows are rewritten by the next pass
 }
 
 // KLT_HIP_FAST (not bit-exact; the tolerance is tests/test_gpu_long.py's):
@@ -537,6 +548,7 @@ __device__ __forceinline__ void wave_exit(int lane, unsigned k) {
 // Level state shared by the passes of one _trackFeature call.
 struct LevState {
   float x2, y2;              // current position (wave-uniform)
+  float pxy;                 // KLT_T7_SOLVE2: the same in lane 0 (x2) and lane 1 (y2), where the solve adds to it
   float aim, agx, agy;       // this lane's img1 samples at (x1, y1), from the first pass
   int it = 0;                // Newton iterations
   int status = kTracked;
@@ -565,6 +577,7 @@ __device__ __forceinline__ int pass7(const TrkArgs &a, const Lev &A, const Lev &
                                      const Lev &R, int &rstat, Counts &cnt, const Carry &cr = Carry{},
                                      unsigned cpx = ~0u) {
   T7_T(t_top);
+  if constexpr (KLT_T7_SOLVE2 && !FIRST) ls.x2 = lane_of(ls.pxy, 0), ls.y2 = lane_of(ls.pxy, 1);
   bool stop = (FIRST && x1_out) || out7(ls.x2, ls.y2, A.tx, A.ty);
   if (BAND && !stop && (band_bad(B, ls.y2) || (FIRST && band_bad(A, y1)))) {
     *a.escape = 1;  // the caller redoes the chunk from whole-frame pyramids
@@ -683,39 +696,73 @@ __device__ __forceinline__ int pass7(const TrkArgs &a, const Lev &A, const Lev &
 #endif
   T7_ADD(0, t_g0);
   T7_T(t_s0);
-  float S[6];
+  // S2L: the exact sums stay in their lanes (row order kSum*) for the two-lane solve
+  constexpr bool S2L = KLT_T7_SOLVE2 && !FAST;
+  constexpr int iXX = S2L ? kSumGxx : 0, iXY = S2L ? kSumGxy : 1, iYY = S2L ? kSumGyy : 2, iEX = S2L ? kSumEx : 3,
+                iEY = S2L ? kSumEy : 4, iRes = S2L ? kSumRes : 5;
+  float S[6], acc = 0.0f;
   if (JOB) {
     const float rb = interp(qr, ri);
-    float v[6] = {gxs * gxs, gxs * gys, gys * gys, dif * gxs, dif * gys, fabsf(pd.aim - rb)};
-    sums<6, FAST, LZ != 0>(red, lane, on, v, S);
+    float v[6];
+    v[iXX] = gxs * gxs, v[iXY] = gxs * gys, v[iYY] = gys * gys, v[iEX] = dif * gxs, v[iEY] = dif * gys;
+    v[iRes] = fabsf(pd.aim - rb);
+    if constexpr (S2L) {
+      acc = sums7_acc<6, LZ != 0>(red, lane, on, v);
+      S[5] = lane_of(acc, kSumRes);
+    } else {
+      sums<6, FAST, LZ != 0>(red, lane, on, v, S);
+    }
     rstat = S[5] / (float)kNpx > a.max_res ? kLargeResidue : (pd.it >= a.max_it ? kMaxIter : kTracked);
     pd.on = false;
     if (rstat != kTracked) return kPassLostPrev;  // that frame's feature is lost: this frame does not happen
   } else {
-    float v[5] = {gxs * gxs, gxs * gys, gys * gys, dif * gxs, dif * gys};
-    float S5[5];
-    sums<5, FAST, LZ != 0>(red, lane, on, v, S5);
+    float v[5];
+    v[iXX] = gxs * gxs, v[iXY] = gxs * gys, v[iYY] = gys * gys, v[iEX] = dif * gxs, v[iEY] = dif * gys;
+    if constexpr (S2L) {
+      acc = sums7_acc<5, LZ != 0>(red, lane, on, v);
+    } else {
+      float S5[5];
+      sums<5, FAST, LZ != 0>(red, lane, on, v, S5);
 #pragma unroll
-    for (int k = 0; k < 5; ++k) S[k] = S5[k];
+      for (int k = 0; k < 5; ++k) S[k] = S5[k];
+    }
   }
   T7_ADD(1, t_s0);
   T7_T(t_v0);
-  // _compute2by2GradientMatrix / _compute2by1ErrorVector / _solveEquation (:227-307)
+  // _compute2by2GradientMatrix / _compute2by1ErrorVector / _solveEquation (:227-307): track7_solve.h
   ++cnt.solves;
-  const float gxx = S[0], gxy = S[1], gyy = S[2];
-  const float ex = S[3] * a.step, ey = S[4] * a.step;
-  const float det = gxx * gyy - gxy * gxy;
+  if constexpr (S2L) S[0] = lane_of(acc, kSumGxx), S[1] = lane_of(acc, kSumGxy), S[2] = lane_of(acc, kSumGyy);
+  const float det = solve_det(S[0], S[1], S[2]);
   if (det < a.min_det) {
     ls.status = kSmallDet;  // x2 has not moved: the post-loop bounds test repeats this pass's
     return kPassDone;
   }
-  const float dx = u((gyy * ex - gxy * ey) / det);
-  const float dy = u((gxx * ey - gxy * ex) / det);
-  ls.x2 = u(ls.x2 + dx);
-  ls.y2 = u(ls.y2 + dy);
+  bool moved;
+  if constexpr (KLT_T7_SOLVE2) {
+    float d;
+    if constexpr (S2L) {
+      d = solve2(acc, S[1], a.step, det);
+    } else {
+      int l = lane;
+      if constexpr (LZ != 0) asm volatile("" : "+v"(l));  // no lane mask kept over the frames (sums7's PIN)
+      const float S5[5] = {S[0], S[1], S[2], S[3], S[4]};
+      d = solve2u(S5, l == 0, a.step, det);
+    }
+    ls.pxy += d;  // read out where it is next needed: no scalar pair held for it through a pass
+    moved = (__ballot(fabsf(d) >= a.min_disp) & 3ull) != 0ull;  // |dx| or |dy|
+  } else {
+    const float S5[5] = {S[0], S[1], S[2], S[3], S[4]};
+    float dx, dy;
+    solve1(S5, a.step, det, dx, dy);
+    dx = u(dx);
+    dy = u(dy);
+    ls.x2 = u(ls.x2 + dx);
+    ls.y2 = u(ls.y2 + dy);
+    moved = fabsf(dx) >= a.min_disp || fabsf(dy) >= a.min_disp;
+  }
   ++ls.it;
   T7_ADD(2, t_v0);
-  return ((fabsf(dx) >= a.min_disp || fabsf(dy) >= a.min_disp) && ls.it < a.max_it) ? kPassAgain : kPassDone;
+  return (moved && ls.it < a.max_it) ? kPassAgain : kPassDone;
 }
 
 // _trackFeature at one level.  Returns the level's status; x2/y2 (uniform)
@@ -733,6 +780,11 @@ __device__ int level7(const TrkArgs &a, const Lev &A, const Lev &B, float x1, fl
   LevState ls;
   ls.x2 = x2;
   ls.y2 = y2;
+  // x2 everywhere, y2 written into lane 1: no lane mask to make or keep.  The
+  // compiler pads no hazard inside the statement, hence the two idle cycles
+  // between the move that writes pxy and the lane write
+  ls.pxy = x2;
+  asm("s_nop 1\n\tv_writelane_b32 %0, %1, 1" : "+v"(ls.pxy) : "s"(y2));
   const Carry none{};
   const Carry &c0 = LZ == 2 ? *cr : none;
   int r = job ? pass7<BAND, true, true, AOS, FAST, LZ>(a, A, B, x1, y1, x1_out, ls, lane, fi, fj, on, red, pd, R, rstat,
@@ -741,6 +793,7 @@ __device__ int level7(const TrkArgs &a, const Lev &A, const Lev &B, float x1, fl
                                                         cnt, c0, cpx);
   while (r == kPassAgain)
     r = pass7<BAND, false, false, AOS, FAST, LZ>(a, A, B, x1, y1, x1_out, ls, lane, fi, fj, on, red, pd, R, rstat, cnt);
+  if constexpr (KLT_T7_SOLVE2) ls.x2 = lane_of(ls.pxy, 0), ls.y2 = lane_of(ls.pxy, 1);
   x2 = ls.x2;
   y2 = ls.y2;
   if constexpr (LZ == 2 && KLT_T7_CARRY && KLT_T7_REUSE) {  // this frame's image 2 is the next frame's image 1
