@@ -47,6 +47,22 @@ void klt_amd_set_reduction(KLT_TrackingContext tc, int reduction);
    or KLT_HIP_FAST sums is a KLTError. */
 #define KLT_AMD_FB_REJECTED -6
 int klt_amd_set_fb_check(KLT_TrackingContext tc, int on, float max_dist);
+/* Motion prior (klt_hip_set_predict in klt_hip.h has the exact definition),
+   off by default: with it on, every frame's search starts from the feature's
+   displacement over the frame before, so that a feature moving steadily by
+   more than the pyramid follows from a zero start is kept.  The tracking
+   context keeps one state per list slot: zero when the setting is turned on
+   (or off), when the list's size changes, for a slot that enters a frame lost
+   or with val > 0 (fresh from selection or replacement), and for a feature
+   lost by a frame.  Honoured by KLTTrackSequence and KLTTrackSequenceReplace
+   (which stay on their batched path) and by KLTTrackFeatures, all in
+   sequential mode, where consecutive calls are consecutive frames; without
+   sequential mode the calls track from a zero start and drop the state.
+   KLTTrackSequences* run their per-sequence loop with it on.  With
+   klt_amd_set_fb_check on, affineConsistencyCheck >= 0 or KLT_HIP_FAST sums a
+   tracking call is a KLTError; so is one with a window other than 7x7 or
+   lighting_insensitive (the device call's refusal).  Returns 0. */
+int klt_amd_set_prediction(KLT_TrackingContext tc, int on);
 
 /* The reference harness loop (example3.c:54-74 without REPLACE) in one call:
      for (i = 1; i < nframes; i++) {

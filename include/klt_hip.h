@@ -239,6 +239,52 @@ int klt_hip_get_fb(klt_hip_ctx *ctx, int *on, float *max_dist);
    the forward step, or by the backward one).  NULL clears it, and so does
    klt_hip_ctx_reset.  The caller keeps the memory valid while it is set. */
 int klt_hip_set_fb_table(klt_hip_ctx *ctx, float *dev_err, long stride);
+/* Motion prior: every frame's search starts from the feature's displacement
+   over the frame before, not from zero motion (the reference starts image 2 at
+   image 1's position, which loses a steadily moving feature once its step
+   passes what the coarsest level's Newton loop reaches).  dev_vx / dev_vy are
+   device arrays of n floats, the state (vx, vy) per feature: read at every
+   tracker launch, written at its end; the caller seeds them (zero: no prior)
+   and keeps them valid while the setting is on.  One frame img1 -> img2 of a
+   feature at (x, y) with status val:
+     1. val != 0 on entry sets the state to (0, 0): val < 0 is lost and not
+        tracked, val > 0 (fresh from selection or replacement) is tracked from
+        a zero prior;
+     2. gx = x + vx, gy = y + vy (one float addition each) go through the
+        divisions by the subsampling as (x, y) does and give image 2's start;
+        image 1's position is unchanged;
+     3. at the coarsest level, after the first multiplication by the
+        subsampling, a start whose window is not inside that level (the
+        tracker's own bounds test; a NaN is not inside) is replaced by image
+        1's position there, the unpredicted start;
+     4. everything else is KLTTrackFeatures as it stands;
+     5. a tracked feature's state becomes (x_new - x, y_new - y), two float
+        subtractions; a lost feature's (0, 0).
+   With an all-zero state the first frame is exactly the plain tracker's.
+   Honoured by klt_hip_track with device arrays, klt_hip_track_sequence,
+   klt_hip_track_frames and klt_hip_track_frames_host (which copies the state
+   into a device block of its own before its first launch and back with the
+   final list, so its arrays may be host arrays as x, y and val are), with or
+   without klt_hip_set_frames_replace (rule 1 covers a replaced slot).
+   Covered: the 7x7 window with KLT_HIP_EXACT sums on fused or generic
+   pyramids of any depth, tracked by the k_track7_pred instances.  They read
+   full level-0 records (klt_hip_set_lazy_grad does not apply) and take the
+   residue pass in place (klt_hip_set_track_merge is ignored).  Refused with -1
+   and a message before any launch, settings and lists untouched: the
+   forward-backward check, the affine check (inside the launch and
+   klt_hip_track_affine), KLT_HIP_FAST sums, any other window,
+   lighting-insensitive mode and the generic tracker (klt_hip_set_track_impl 1,
+   klt_hip_set_track_patch 0, klt_hip_set_prof), klt_hip_track_frames_band and
+   the sharded drivers, the multi-sequence calls (klt_hip_multi_covers returns
+   -1 as well), klt_hip_track with host arrays.  on = 0 clears the arrays;
+   klt_hip_ctx_reset turns the setting off. */
+int klt_hip_set_predict(klt_hip_ctx *ctx, int on, float *dev_vx, float *dev_vy);
+int klt_hip_get_predict(klt_hip_ctx *ctx, int *on, float **dev_vx, float **dev_vy);
+/* optional device tables of the state with the prior on: row f (stride
+   elements apart, stride >= n) receives the state after tracked frame f, rows
+   counted as klt_hip_set_fb_table's.  Both or neither; NULL clears them, and
+   so does klt_hip_ctx_reset. */
+int klt_hip_set_predict_table(klt_hip_ctx *ctx, float *dev_tab_vx, float *dev_tab_vy, long stride);
 /* tuning hook: 1 (default) raises the tracker waves' issue priority
    (s_setprio 3) so that, when the next chunk's pyramids are built beside the
    tracker (overlapped schedule, band calls with build-ahead), a feature's

@@ -51,6 +51,10 @@ typedef struct {
   int reduction; /* KLT_HIP_EXACT unless KLT_AMD_REDUCTION=fast */
   int fb_on;     /* forward-backward check (klt_amd_set_fb_check), applied to the device context per call */
   float fb_dist;
+  /* motion prior (klt_amd_set_prediction): one state (vx, vy) per list slot,
+     zero when the setting is turned on or the list size changes */
+  int pred_on, pred_n;
+  float *pred_vx, *pred_vy;
   /* affine consistency check: the feature list whose stored windows the
      device store holds, and per slot the aff_img whose data it holds */
   KLT_FeatureList aff_list;
@@ -61,6 +65,7 @@ typedef struct {
 #define FULL(tc) ((klt_ctx_full *)(tc))
 
 enum { SLOT_A = 0, SLOT_B = 1, SLOT_SELECT = 2 };
+enum { MEMCPY_H2D = 1, MEMCPY_D2H = 2 }; /* klt_hip_memcpy's kinds (hipMemcpyKind) */
 
 /* Device contexts of freed tracking contexts are kept (reset, allocations
    intact) and handed to the next tracking context on the same device, so a
@@ -158,6 +163,46 @@ static void apply_fb(KLT_TrackingContext tc, const char *who)
   if (f->fb_on && f->reduction != KLT_HIP_EXACT)
     KLTError("(%s) the forward-backward check needs exact sums (KLT_HIP_EXACT)", who);
   dev_check(tc, klt_hip_set_fb(device_of(tc), f->fb_on, f->fb_dist), "forward-backward setting");
+}
+
+/* The motion prior of this tracking context, before every tracking call: the
+   combinations it does not cover are errors, as FB with the affine check is;
+   off on the device context until a call that carries the state turns it on
+   (pred_begin).  Returns 1 when the call tracks with the prior: the setting is
+   on and, for the per-call and per-frame-loop paths, the mode is sequential
+   (consecutive calls are then consecutive frames). */
+static int apply_pred(KLT_TrackingContext tc, const char *who)
+{
+  klt_ctx_full *f = FULL(tc);
+  if (f->pred_on && f->fb_on) KLTError("(%s) the motion prior does not combine with the forward-backward check", who);
+  if (f->pred_on && tc->affineConsistencyCheck >= 0)
+    KLTError("(%s) the motion prior does not combine with affineConsistencyCheck=%d", who,
+             tc->affineConsistencyCheck);
+  if (f->pred_on && f->reduction != KLT_HIP_EXACT)
+    KLTError("(%s) the motion prior needs exact sums (KLT_HIP_EXACT)", who);
+  dev_check(tc, klt_hip_set_predict(device_of(tc), 0, NULL, NULL), "motion prior setting");
+  return f->pred_on && tc->sequentialMode;
+}
+
+/* the state arrays for a list of n slots: kept from call to call, zeroed when n changes */
+static void pred_state(KLT_TrackingContext tc, int n)
+{
+  klt_ctx_full *f = FULL(tc);
+  if (f->pred_vx && f->pred_n == n) return;
+  free(f->pred_vx);
+  free(f->pred_vy);
+  f->pred_vx = (float *)calloc((size_t)n + 1, sizeof(float));
+  f->pred_vy = (float *)calloc((size_t)n + 1, sizeof(float));
+  if (!f->pred_vx || !f->pred_vy) KLTError("(klt_amd_set_prediction) Out of memory");
+  f->pred_n = n;
+}
+
+static void pred_drop(klt_ctx_full *f)
+{
+  free(f->pred_vx);
+  free(f->pred_vy);
+  f->pred_vx = f->pred_vy = NULL;
+  f->pred_n = 0;
 }
 
 /* ------------------------------------------------------------------ */
@@ -379,6 +424,7 @@ EXPORT void KLTFreeTrackingContext(KLT_TrackingContext tc)
   f = FULL(tc);
   release_device(f->dev);
   free(f->aff_owner);
+  pred_drop(f);
   free(f);
 }
 
@@ -886,7 +932,7 @@ EXPORT void KLTTrackFeatures(KLT_TrackingContext tc, KLT_PixelType *img1, KLT_Pi
   klt_hip_ctx *dev;
   klt_hip_pyr_desc d;
   klt_hip_track_desc td;
-  int slot1, slot2, k, n = fl->nFeatures;
+  int slot1, slot2, k, pred, n = fl->nFeatures;
   float *x, *y;
   int *v;
 
@@ -899,6 +945,8 @@ EXPORT void KLTTrackFeatures(KLT_TrackingContext tc, KLT_PixelType *img1, KLT_Pi
   affine_check_tc(tc);
   dev = device_of(tc);
   apply_fb(tc, "KLTTrackFeatures");
+  pred = apply_pred(tc, "KLTTrackFeatures");
+  if (FULL(tc)->pred_on && !pred) pred_drop(FULL(tc)); /* not sequential: no frame before this one */
 
   if (tc->sequentialMode && tc->pyramid_last != NULL && f->last_slot >= 0) {
     if (f->last_w != ncols || f->last_h != nrows)
@@ -948,7 +996,30 @@ EXPORT void KLTTrackFeatures(KLT_TrackingContext tc, KLT_PixelType *img1, KLT_Pi
   if (tc->affineConsistencyCheck >= 0) {
     track_affine(tc, fl, slot1, slot2, &td, x, y, v);
   } else {
-    dev_check(tc, klt_hip_track(dev, slot1, slot2, &td, x, y, v, n, 0), "feature tracking");
+    if (pred && n > 0) {
+      /* the prior's kernels take the list and the state in device memory */
+      const size_t nb = sizeof(float) * (size_t)n;
+      float *d = (float *)klt_hip_malloc(dev, 5 * nb);
+      int rc;
+      if (!d) KLTError("(KLTTrackFeatures) device memory for the motion prior: %s", klt_hip_last_error(dev));
+      pred_state(tc, n);
+      rc = klt_hip_memcpy(dev, d, x, nb, MEMCPY_H2D) || klt_hip_memcpy(dev, d + n, y, nb, MEMCPY_H2D) ||
+           klt_hip_memcpy(dev, d + 2 * (size_t)n, v, nb, MEMCPY_H2D) ||
+           klt_hip_memcpy(dev, d + 3 * (size_t)n, f->pred_vx, nb, MEMCPY_H2D) ||
+           klt_hip_memcpy(dev, d + 4 * (size_t)n, f->pred_vy, nb, MEMCPY_H2D) ||
+           klt_hip_set_predict(dev, 1, d + 3 * (size_t)n, d + 4 * (size_t)n);
+      if (!rc) rc = klt_hip_track(dev, slot1, slot2, &td, d, d + n, (int *)(d + 2 * (size_t)n), n, 1);
+      klt_hip_set_predict(dev, 0, NULL, NULL); /* off again, whatever the call returned */
+      if (!rc)
+        rc = klt_hip_memcpy(dev, x, d, nb, MEMCPY_D2H) || klt_hip_memcpy(dev, y, d + n, nb, MEMCPY_D2H) ||
+             klt_hip_memcpy(dev, v, d + 2 * (size_t)n, nb, MEMCPY_D2H) ||
+             klt_hip_memcpy(dev, f->pred_vx, d + 3 * (size_t)n, nb, MEMCPY_D2H) ||
+             klt_hip_memcpy(dev, f->pred_vy, d + 4 * (size_t)n, nb, MEMCPY_D2H);
+      dev_check(tc, rc, "feature tracking");
+      klt_hip_free(dev, d);
+    } else {
+      dev_check(tc, klt_hip_track(dev, slot1, slot2, &td, x, y, v, n, 0), "feature tracking");
+    }
     for (k = 0; k < n; k++) {
       KLT_Feature ft = fl->feature[k];
       if (ft->val < 0) continue; /* untouched, like the reference (:1346) */
@@ -1027,7 +1098,7 @@ static void track_sequence(KLT_TrackingContext tc, KLT_PixelType **frames, int n
   klt_hip_track_desc td;
   taps_state st, after1;
   store_rows_ctx sr;
-  int k, i, seq_start, steady, seed_first, n = fl->nFeatures, T = nframes - 1;
+  int k, i, seq_start, steady, seed_first, pred, n = fl->nFeatures, T = nframes - 1;
   const int affine = tc->affineConsistencyCheck >= 0;
   affine_io aio;
   const unsigned char *const *src;
@@ -1045,6 +1116,7 @@ static void track_sequence(KLT_TrackingContext tc, KLT_PixelType **frames, int n
     KLTError("(KLTStoreFeatures) FeatureList and FeatureTable must have the same number of features");
   dev = device_of(tc);
   apply_fb(tc, every ? "KLTTrackSequenceReplace" : "KLTTrackSequence");
+  pred = apply_pred(tc, every ? "KLTTrackSequenceReplace" : "KLTTrackSequence");
   seq_start = tc->sequentialMode && tc->pyramid_last != NULL && f->last_slot >= 0;
   if (seq_start && (f->last_w != ncols || f->last_h != nrows))
     KLTError("(KLTTrackSequence) Size of incoming image (%d by %d) is different from size of "
@@ -1069,6 +1141,8 @@ static void track_sequence(KLT_TrackingContext tc, KLT_PixelType **frames, int n
      selection image of frames[i] through the kernel cache), and does not
      combine with the affine check */
   if (every && (!tc->sequentialMode || affine)) steady = 0;
+  /* the prior is kept from call to call in sequential mode only (KLTTrackFeatures): the loop ignores it */
+  if (f->pred_on && !pred) steady = 0;
   if (!steady) {
     for (i = 1; i < nframes; i++) {
       KLTTrackFeatures(tc, frames[i - 1], frames[i], ncols, nrows, fl);
@@ -1119,6 +1193,10 @@ static void track_sequence(KLT_TrackingContext tc, KLT_PixelType **frames, int n
   }
   sr.ft = ft;
   sr.col = ft_col;
+  if (pred) { /* the state goes up and comes back with the list (klt_hip_track_frames_host) */
+    pred_state(tc, n);
+    dev_check(tc, klt_hip_set_predict(dev, 1, f->pred_vx, f->pred_vy), "motion prior setting");
+  }
   if (affine) {
     /* the check runs inside the tracker launch (klt_hip_set_frames_affine) on
        device copies of the list's affine state; the list ends as the per-call
@@ -1155,6 +1233,7 @@ static void track_sequence(KLT_TrackingContext tc, KLT_PixelType **frames, int n
                                    hy, hv, n, ft ? store_rows : NULL, &sr);
     if (rc == 0) rc = klt_hip_frames_replace_changed(dev, changed, n);
     klt_hip_set_frames_replace(dev, NULL); /* off again, whatever the call returned */
+    klt_hip_set_predict(dev, 0, NULL, NULL);
     dev_check(tc, rc, "sequence tracking");
     /* a slot lost on entry that no replacement wrote stays untouched (:1346);
        a written one got mark_found's treatment when it was written */
@@ -1171,9 +1250,10 @@ static void track_sequence(KLT_TrackingContext tc, KLT_PixelType **frames, int n
     free(changed);
     free(skip);
   } else {
-    dev_check(tc, klt_hip_track_frames_host(dev, &d2, &td, src, seed_first ? nframes : nframes - 1, seed_first,
-                                            SEQ_CHUNK, hx, hy, hv, n, ft ? store_rows : NULL, &sr),
-              "sequence tracking");
+    const int rc = klt_hip_track_frames_host(dev, &d2, &td, src, seed_first ? nframes : nframes - 1, seed_first,
+                                             SEQ_CHUNK, hx, hy, hv, n, ft ? store_rows : NULL, &sr);
+    klt_hip_set_predict(dev, 0, NULL, NULL); /* off again, whatever the call returned */
+    dev_check(tc, rc, "sequence tracking");
     for (k = 0; k < n; k++) {
       KLT_Feature ftr = fl->feature[k];
       if (ftr->val < 0) continue; /* untouched, like the reference (:1346) */
@@ -1239,11 +1319,11 @@ static KLT_TrackingContext fresh_copy(KLT_TrackingContext tc)
   g->reduction = FULL(tc)->reduction;
   g->fb_on = FULL(tc)->fb_on;
   g->fb_dist = FULL(tc)->fb_dist;
+  g->pred_on = FULL(tc)->pred_on; /* its state starts at zero */
   return t;
 }
 
 #define MULTI_STAGE_BYTES ((size_t)256 << 20) /* pinned staging of one group of frames, at most */
-enum { MEMCPY_H2D = 1, MEMCPY_D2H = 2 };      /* klt_hip_memcpy's kinds (hipMemcpyKind) */
 
 /* every == 0: KLTTrackSequences; every >= 1: KLTTrackSequencesReplace, the same
    call with KLTReplaceLostFeatures after every `every`-th tracked frame of
@@ -1286,7 +1366,8 @@ static void track_sequences(KLT_TrackingContext tc, KLT_PixelType ***frames, int
      its batched path from its own frames[0] with one and the same pyramid
      description: the dry run of its kernel-cache lookups, sequence after
      sequence as the loop would make them */
-  multi = nseq <= KLT_HIP_MAX_SEQUENCES && tc->affineConsistencyCheck < 0 && !f->fb_on && !tc->writeInternalImages;
+  multi = nseq <= KLT_HIP_MAX_SEQUENCES && tc->affineConsistencyCheck < 0 && !f->fb_on && !f->pred_on &&
+          !tc->writeInternalImages;
   /* the batched replacement reads the tracked frame's own pyramid: sequential mode only (track_sequence) */
   if (every && !tc->sequentialMode) multi = 0;
   pthread_mutex_lock(&g_taps_lock);
@@ -1524,6 +1605,13 @@ EXPORT void klt_amd_track_desc(KLT_TrackingContext tc, klt_hip_track_desc *td)
 EXPORT void klt_amd_set_reduction(KLT_TrackingContext tc, int reduction)
 {
   FULL(tc)->reduction = reduction;
+}
+
+EXPORT int klt_amd_set_prediction(KLT_TrackingContext tc, int on)
+{
+  FULL(tc)->pred_on = on ? 1 : 0;
+  pred_drop(FULL(tc)); /* the state starts at zero (pred_state) */
+  return 0;
 }
 
 EXPORT int klt_amd_set_fb_check(KLT_TrackingContext tc, int on, float max_dist)

@@ -197,6 +197,13 @@ struct TrkFbArgs {
   long stride;  // its row stride (elements)
 };
 constexpr int kFbRejected = KLT_HIP_FB_REJECTED;
+// motion prior (klt_hip_set_predict): the prediction instances of k_track7 take
+// this beside TrkFramesArgs, so the others keep their argument layout
+struct TrkPredArgs {
+  float *vx, *vy;    // per feature: its displacement over the last tracked frame (in/out)
+  float *tvx, *tvy;  // optional tables: row j receives the state after frame j; nullptr: none
+  long tstride;      // their row stride (elements)
+};
 // several independent sequences in one launch (klt_hip_track_frames_multi):
 // the multi instances take this beside TrkFramesArgs, so the others keep
 // their argument layout.  Sequence s owns features [first[s], first[s + 1]) of
@@ -339,8 +346,13 @@ hipError_t launch_track_frames(hipStream_t st, bool exact, bool li, bool patch, 
 size_t track_affine_lds_bytes(int mode);
 // track7.hip: the default configuration (7x7 window, exact sums, no gain/bias,
 // one wave per feature) with the latency-lean pass; band: escape checks
+// pr != nullptr: the motion-prior instances (exact sums, whole frames, not together with fb)
 hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y,
-                         int *v, int n, const char **name = nullptr, const TrkFbArgs *fb = nullptr);
+                         int *v, int n, const char **name = nullptr, const TrkFbArgs *fb = nullptr,
+                         const TrkPredArgs *pr = nullptr);
+// track7_pred.hip: the k_track7_pred instances, for launch_track7 (a with the bounds thresholds, its grid and depth)
+hipError_t launch_track7_pred(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkPredArgs &pr, float *x,
+                              float *y, int *v, int n, int grid, bool two, const char **name);
 // the multi-sequence instances (whole-frame interleaved pyramids, exact sums)
 hipError_t launch_track7_multi(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkMultiArgs &m, float *x,
                                float *y, int *v, int n, const char **name = nullptr);

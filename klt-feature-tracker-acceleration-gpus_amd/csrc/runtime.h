@@ -175,6 +175,15 @@ struct __attribute__((visibility("default"))) klt_hip_ctx {  // its constructor 
   float fb_dist = 0.0f;
   float *fb_tab = nullptr;
   long fb_stride = 0;
+  // motion prior (klt_hip_set_predict): off by default; the caller's device
+  // state arrays, the optional device tables (klt_hip_set_predict_table), and
+  // the staging of klt_hip_track_frames_host (vx | vy)
+  int pred_on = 0;
+  float *pred_vx = nullptr, *pred_vy = nullptr;
+  float *pred_tvx = nullptr, *pred_tvy = nullptr;
+  long pred_stride = 0;
+  float *d_pred = nullptr;
+  size_t pred_cap = 0;
   // affine check inside the tracker launch (klt_hip_set_frames_affine): the
   // caller's device arrays, the optional tables (klt_hip_set_affine_table);
   // aff_fresh: the next tracker launch is the first of its API call (windows
@@ -471,6 +480,7 @@ int order_features(klt_hip_ctx *c, hipStream_t st, int nrows, const float *y, co
                    const float *own, TrkFramesArgs &bb);
 int fb_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const char *who);
 int aff_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, int n, const char *who);
+int pred_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const char *who);
 int track_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, int n, const char *who);
 int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc *d, const TrkArgs &a,
                         const TrkFramesArgs &b, float *x, float *y, int *v, int n, const float *own = nullptr,

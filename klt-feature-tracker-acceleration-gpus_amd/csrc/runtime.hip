@@ -211,6 +211,7 @@ KLT_API void klt_hip_ctx_destroy(klt_hip_ctx *c) {
   if (c->h_feat) hipHostFree(c->h_feat);
   hipFree(c->d_eig);
   hipFree(c->d_rep_map);
+  hipFree(c->d_pred);
   if (c->h_rep) hipHostFree(c->h_rep);
   if (c->ev_rep) hipEventDestroy(c->ev_rep);
   sel_engine_destroy(c->sel);
@@ -315,6 +316,10 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->fb_dist = 0.0f;
   c->fb_tab = nullptr;
   c->fb_stride = 0;
+  c->pred_on = 0;
+  c->pred_vx = c->pred_vy = nullptr;
+  c->pred_tvx = c->pred_tvy = nullptr;
+  c->pred_stride = 0;
   c->aff_on = 0;
   c->aff_dev = nullptr;
   c->aff_state_dev = nullptr;
@@ -649,6 +654,33 @@ KLT_API int klt_hip_set_fb_table(klt_hip_ctx *c, float *dev_err, long stride) {
   if (dev_err && stride < 1) return fail(c, "set_fb_table: stride %ld < 1", stride);
   c->fb_tab = dev_err;
   c->fb_stride = dev_err ? stride : 0;
+  return 0;
+}
+
+KLT_API int klt_hip_set_predict(klt_hip_ctx *c, int on, float *dev_vx, float *dev_vy) {
+  if (!c) return fail(c, "set_predict: null context");
+  if (on && (!dev_vx || !dev_vy)) return fail(c, "set_predict: null state array");
+  c->pred_on = on ? 1 : 0;
+  c->pred_vx = on ? dev_vx : nullptr;
+  c->pred_vy = on ? dev_vy : nullptr;
+  return 0;
+}
+
+KLT_API int klt_hip_get_predict(klt_hip_ctx *c, int *on, float **dev_vx, float **dev_vy) {
+  if (!c) return fail(c, "get_predict: null context");
+  if (on) *on = c->pred_on;
+  if (dev_vx) *dev_vx = c->pred_vx;
+  if (dev_vy) *dev_vy = c->pred_vy;
+  return 0;
+}
+
+KLT_API int klt_hip_set_predict_table(klt_hip_ctx *c, float *dev_tab_vx, float *dev_tab_vy, long stride) {
+  if (!c) return fail(c, "set_predict_table: null context");
+  if ((dev_tab_vx != nullptr) != (dev_tab_vy != nullptr)) return fail(c, "set_predict_table: give both tables or none");
+  if (dev_tab_vx && stride < 1) return fail(c, "set_predict_table: stride %ld < 1", stride);
+  c->pred_tvx = dev_tab_vx;
+  c->pred_tvy = dev_tab_vy;
+  c->pred_stride = dev_tab_vx ? stride : 0;
   return 0;
 }
 

@@ -327,10 +327,10 @@ FramesPlan plan_layout(klt_hip_ctx *c, const FramesCall &q) {
   // level 0 of the banks as the img plane alone, its gradients computed by the
   // tracker for the windows it reads (klt_hip_set_lazy_grad): whole-frame fused
   // pyramids tracked by k_track7 (its fast-sum instance: two levels) without
-  // the forward-backward check, from a previous pyramid that is interleaved
+  // the forward-backward check or the motion prior, from a previous pyramid that is interleaved
   // or image-only itself.  Any other call first makes an image-only previous
   // pyramid whole.
-  p.lazy = c->lazy_grad && p.fz && t7 && !band && !c->fb_on && !c->aff_on &&
+  p.lazy = c->lazy_grad && p.fz && t7 && !band && !c->fb_on && !c->aff_on && !c->pred_on &&
            (q.td->reduction == KLT_HIP_EXACT || pd->nlevels == 2) && prev_level(c, 0).il != kLayoutPlanes;
   // the banks' layout follows their reader: interleaved for k_track7 (level 0
   // the img plane alone for its lazy-gradient instance), planes for the
@@ -839,12 +839,51 @@ int host_pipeline_prepare(klt_hip_ctx *c, size_t stage_bytes, size_t rows_bytes)
 }
 }  // namespace
 
+namespace {
+// klt_hip_track_frames_host with the motion prior on: the launches read and
+// write the context's own device block (vx | vy), filled from the caller's
+// arrays before the first one and copied back to them after the last; the
+// setting points at the caller's arrays again however the call ends
+struct PredStage {
+  klt_hip_ctx *c;
+  int n;
+  float *vx, *vy;  // the caller's arrays; null: the setting is off, or no features
+  PredStage(klt_hip_ctx *c_, int n_) : c(c_), n(n_), vx(nullptr), vy(nullptr) {
+    if (c->pred_on && n > 0) vx = c->pred_vx, vy = c->pred_vy;
+  }
+  ~PredStage() {
+    if (vx) c->pred_vx = vx, c->pred_vy = vy;
+  }
+  PredStage(const PredStage &) = delete;
+  PredStage &operator=(const PredStage &) = delete;
+  int up() const {
+    if (!vx) return 0;
+    if (grow(c, &c->d_pred, &c->pred_cap, 2 * (size_t)n)) return -1;
+    const size_t nb = sizeof(float) * (size_t)n;
+    HIPCHK(c, hipMemcpyAsync(c->d_pred, vx, nb, hipMemcpyDefault, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_pred + n, vy, nb, hipMemcpyDefault, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's arrays may be pageable: read by now
+    c->pred_vx = c->d_pred;
+    c->pred_vy = c->d_pred + n;
+    return 0;
+  }
+  int down() const {
+    if (!vx) return 0;
+    const size_t nb = sizeof(float) * (size_t)n;
+    HIPCHK(c, hipMemcpyAsync(vx, c->d_pred, nb, hipMemcpyDefault, c->stream));
+    HIPCHK(c, hipMemcpyAsync(vy, c->d_pred + n, nb, hipMemcpyDefault, c->stream));
+    return 0;  // feat_unpack waits for the stream
+  }
+};
+}  // namespace
+
 KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td,
                                       const unsigned char *const *frames, int nframes, int seed_first, int chunk,
                                       float *x, float *y, int *val, int n, klt_hip_rows_fn rows, void *user) {
   if (!c || !pd || !td || (nframes > 0 && !frames)) return fail(c, "track_frames_host: null argument");
   if (chunk < 1 || nframes < 0 || n < 0) return fail(c, "track_frames_host: bad nframes/chunk/n");
   const GrayFrames gray_ring(c);  // host frames are gray: so is the upload ring the calls below read
+  if (pred_refused(c, td, false, "track_frames_host")) return -1;
   if (fb_refused(c, td, false, "track_frames_host")) return -1;
   if (aff_refused(c, td, false, n, "track_frames_host")) return -1;
   if (c->rep_on && c->aff_on)
@@ -869,6 +908,10 @@ KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
   if (n > 0 && feat_stage_in(c, x, y, val, n)) return -1;
   float *dx = c->d_fx, *dy = c->d_fy;
   int *dv = c->d_fv;
+  // the motion prior's state goes up with the list and comes back with it
+  // (the caller's arrays may be host arrays here, as x, y and val are)
+  const PredStage pred_stage(c, n);
+  if (pred_stage.up()) return -1;
   // the ring and the rows slots may still be read by earlier work on the context stream
   for (int k = 0; k < 2; ++k) {
     HIPCHK(c, hipEventRecord(c->ev_ring_free[k], c->stream));
@@ -963,6 +1006,7 @@ KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
   tr.mark(SeqStages::LAUNCH);
   if (n > 0) {
     HIPCHK(c, hipMemcpyAsync(c->h_feat, c->d_feat, 3 * sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+    if (pred_stage.down()) return -1;
     if (feat_unpack(c, x, y, val, n)) return -1;
   }
   tr.mark(SeqStages::TAIL);

@@ -29,6 +29,7 @@ namespace {
 int multi_refused(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td, const char *who) {
   if (c->fb_on) return fail(c, "%s: the forward-backward check is not covered (klt_hip_set_fb)", who);
   if (c->aff_on) return fail(c, "%s: the affine check is not covered (klt_hip_set_frames_affine)", who);
+  if (c->pred_on) return fail(c, "%s: the motion prior is not covered (klt_hip_set_predict)", who);
   if (td->reduction != KLT_HIP_EXACT) return fail(c, "%s: needs KLT_HIP_EXACT sums", who);
   if (td->window_width != 7 || td->window_height != 7)
     return fail(c, "%s: window %dx%d is not covered (7x7 only)", who, td->window_width, td->window_height);
@@ -295,6 +296,7 @@ int track_multi(klt_hip_ctx *c, const char *who, const klt_hip_pyr_desc *pd, con
 
 KLT_API int klt_hip_multi_covers(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td) {
   if (!c || !pd || !td) return fail(c, "multi_covers: null argument");
+  if (c->pred_on) return fail(c, "track_frames_multi: the motion prior is not covered (klt_hip_set_predict)");
   return multi_refused(c, pd, td, "track_frames_multi") ? 0 : 1;
 }
 

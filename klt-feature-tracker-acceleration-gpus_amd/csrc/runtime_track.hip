@@ -177,14 +177,37 @@ int aff_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, int n, c
   return 0;
 }
 
-// both of the above, and the forward-backward table's rows hold n features:
+// The motion prior (klt_hip_set_predict) has instances of k_track7 for exact
+// sums on whole-frame pyramids, without either check: anything else fails
+// before a launch.
+int pred_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const char *who) {
+  if (!c->pred_on) return 0;
+  if (band) return fail(c, "%s: the motion prior does not cover band calls (klt_hip_set_predict)", who);
+  if (d->reduction != KLT_HIP_EXACT)
+    return fail(c, "%s: the motion prior needs KLT_HIP_EXACT sums (klt_hip_set_predict)", who);
+  if (c->fb_on)
+    return fail(c, "%s: the forward-backward check does not combine with the motion prior "
+                "(klt_hip_set_fb, klt_hip_set_predict)", who);
+  if (c->aff_on)
+    return fail(c, "%s: the affine check does not combine with the motion prior "
+                "(klt_hip_set_frames_affine, klt_hip_set_predict)", who);
+  if (!t7_tracks(c, d))
+    return fail(c, "%s: the motion prior needs the default tracker kernel: a 7x7 window without lighting-insensitive "
+                "mode (klt_hip_set_predict; klt_hip_set_track_impl 0, klt_hip_set_track_patch 1, no klt_hip_set_prof "
+                "buffer)", who);
+  return 0;
+}
+
+// all of the above, and the tables' rows hold n features:
 // what a tracker launch of n features in the name of `who` refuses.  An entry
 // point that hands its work to another one asks the two above alone and
 // leaves the table to the launch underneath, in that one's name
 int track_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, int n, const char *who) {
-  if (fb_refused(c, d, band, who) || aff_refused(c, d, band, n, who)) return -1;
+  if (pred_refused(c, d, band, who) || fb_refused(c, d, band, who) || aff_refused(c, d, band, n, who)) return -1;
   if (c->fb_on && c->fb_tab && c->fb_stride < n)
     return fail(c, "%s: forward-backward table stride %ld < n %d", who, c->fb_stride, n);
+  if (c->pred_on && c->pred_tvx && c->pred_stride < n)
+    return fail(c, "%s: motion prior table stride %ld < n %d", who, c->pred_stride, n);
   return 0;
 }
 
@@ -243,6 +266,15 @@ int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc
     fb.stride = c->fb_stride;
   }
   const TrkFbArgs *fbp = c->fb_on ? &fb : nullptr;
+  TrkPredArgs pr{};
+  if (c->pred_on) {  // track_refused: t7, exact sums
+    pr.vx = c->pred_vx;
+    pr.vy = c->pred_vy;
+    pr.tvx = c->pred_tvx ? c->pred_tvx + fb_row * c->pred_stride : nullptr;
+    pr.tvy = c->pred_tvy ? c->pred_tvy + fb_row * c->pred_stride : nullptr;
+    pr.tstride = c->pred_stride;
+  }
+  const TrkPredArgs *prp = c->pred_on ? &pr : nullptr;
   if (t7) {
     // the lazy-gradient instances have twins that count and take times
     if (aa.lazy && aa.aos) bb.wave_t = c->wave_t;
@@ -258,7 +290,7 @@ int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc
       }
     }
     const int rc =
-        launched(c, "k_track7", launch_track7(st, aa.escape != nullptr, aa, b2, x, y, v, n, &c->track_kernel, fbp));
+        launched(c, "k_track7", launch_track7(st, aa.escape != nullptr, aa, b2, x, y, v, n, &c->track_kernel, fbp, prp));
     if (rc && tail && tail->wait) {  // counted on the host, maybe not on the device: no wait, and re-base next time
       tail->wait = false;
       c->exits_base = kExitsRebase + 1;
@@ -426,7 +458,11 @@ KLT_API int klt_hip_track(klt_hip_ctx *c, int s1, int s2, const klt_hip_track_de
   for (int l = 0; l < A.nlev; ++l)
     if (A.lv[l].w != B.lv[l].w || A.lv[l].h != B.lv[l].h) return fail(c, "track: slot size mismatch");
   if (check_window(c, d)) return -1;
-  if (fb_refused(c, d, false, "track")) return -1;
+  if (pred_refused(c, d, false, "track") || fb_refused(c, d, false, "track")) return -1;
+  if (c->pred_on && !on_device)
+    return fail(c, "track: the motion prior takes device arrays (on_device = 1; klt_hip_set_predict)");
+  if (c->pred_on && c->pred_tvx && c->pred_stride < n)
+    return fail(c, "track: motion prior table stride %ld < n %d", c->pred_stride, n);
   if (c->aff_on && !on_device)
     return fail(c, "track: the affine check inside the launch takes device arrays (on_device = 1; "
                 "klt_hip_set_frames_affine)");
@@ -545,6 +581,8 @@ KLT_API int klt_hip_track_affine(klt_hip_ctx *c, int s1, int s2, const klt_hip_t
   if (c->aff_on)
     return fail(c, "track_affine: the affine check is set to run inside the tracker launch "
                 "(klt_hip_set_frames_affine); turn that off for per-call checks");
+  if (c->pred_on)
+    return fail(c, "track_affine: the affine check does not combine with the motion prior (klt_hip_set_predict)");
   if (n <= 0) return 0;
   if (s1 < 0 || s1 >= KLT_HIP_MAX_SLOTS || s2 < 0 || s2 >= KLT_HIP_MAX_SLOTS)
     return fail(c, "track_affine: bad slot");
@@ -619,7 +657,9 @@ KLT_API int klt_hip_track_sequence(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, c
   if (c->rep_on)
     return fail(c, "track_sequence: not covered while lost features are replaced (klt_hip_set_frames_replace)");
   if (nsteps <= 0) return 0;
-  if (fb_refused(c, td, false, "track_sequence") || aff_refused(c, td, false, n, "track_sequence")) return -1;
+  if (pred_refused(c, td, false, "track_sequence") || fb_refused(c, td, false, "track_sequence") ||
+      aff_refused(c, td, false, n, "track_sequence"))
+    return -1;
   AffCall aff_call(c);
   if (use_device(c)) return -1;
   if (ensure_pipeline(c)) return -1;

@@ -734,6 +734,9 @@ KLT_API int klt_shard_track(klt_shard *s, const klt_hip_pyr_desc *pd, const klt_
     return sfail(s, "shard_track: bad frames or feature arrays");
   if (klt_hip_get_frame_format(s->ctx) != KLT_HIP_FRAME_GRAY8)
     return sfail(s, "shard_track: colour frames are not covered (klt_hip_set_frame_format); convert with klt_hip_to_gray");
+  int pred_on = 0;
+  if (klt_hip_get_predict(s->ctx, &pred_on, nullptr, nullptr) == 0 && pred_on)
+    return sfail(s, "shard_track: the motion prior does not cover band calls (klt_hip_set_predict)");
   DeviceGuard guard;
   if (hipSetDevice(klt_hip_ctx_device(s->ctx)) != hipSuccess) return abort_comm(s, "shard_track: device");
   hipStream_t st = (hipStream_t)klt_hip_get_stream(s->ctx);

@@ -38,6 +38,9 @@
 
 #include "klt_dev.h"
 
+#ifndef KLT_T7_PRED_UNIT
+#define KLT_T7_PRED_UNIT 0  // 1: included by track7_pred.hip, which holds the k_track7_pred instances alone
+#endif
 #ifndef KLT_T7_NL2
 #define KLT_T7_NL2 1  // the two-level instances (A/B hook: 0 launches the runtime-depth ones)
 #endif
@@ -862,9 +865,10 @@ __global__ __launch_bounds__(kBlock, LAZY && NL == 2 ? 5 : LAZY ? 4 : 1) void k_
                                                    float *__restrict__ fy, int *__restrict__ fv, int n) {
   static_assert(!LAZY || (AOS && !BAND), "lazy gradients: whole-frame interleaved pyramids");
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF + (LAZY ? kPat : 0)];
-  constexpr bool FB = false, HOOK = false, MULTI = false;
+  constexpr bool FB = false, HOOK = false, MULTI = false, PRED = false;
   const TrkFbArgs fb{};
   const TrkMultiArgs ms{};
+  const TrkPredArgs pr{};
 #include "track7_body.h"
 }
 
@@ -877,9 +881,10 @@ __global__ __launch_bounds__(kBlock, NL == 2 ? 5 : 4) void k_track7_hook(TrkArgs
                                                                           float *__restrict__ fy,
                                                                           int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF + kPat];
-  constexpr bool BAND = false, AOS = true, LAZY = true, FB = false, HOOK = true, MULTI = false;
+  constexpr bool BAND = false, AOS = true, LAZY = true, FB = false, HOOK = true, MULTI = false, PRED = false;
   const TrkFbArgs fb{};
   const TrkMultiArgs ms{};
+  const TrkPredArgs pr{};
 #include "track7_body.h"
 }
 
@@ -889,8 +894,9 @@ __global__ __launch_bounds__(kBlock) void k_track7_fb(TrkArgs a, TrkFramesArgs b
                                                       float *__restrict__ fx, float *__restrict__ fy,
                                                       int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
-  constexpr bool BAND = false, FAST = false, FB = true, LAZY = false, HOOK = false, MULTI = false;
+  constexpr bool BAND = false, FAST = false, FB = true, LAZY = false, HOOK = false, MULTI = false, PRED = false;
   const TrkMultiArgs ms{};
+  const TrkPredArgs pr{};
 #include "track7_body.h"
 }
 
@@ -905,8 +911,30 @@ __global__ __launch_bounds__(kBlock) void k_track7_multi(TrkArgs a, TrkFramesArg
                                                          float *__restrict__ fx, float *__restrict__ fy,
                                                          int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
-  constexpr bool BAND = false, AOS = true, FAST = false, FB = false, LAZY = false, HOOK = false, MULTI = true;
+  constexpr bool BAND = false, AOS = true, FAST = false, FB = false, LAZY = false, HOOK = false, MULTI = true,
+                 PRED = false;
   const TrkFbArgs fb{};
+  const TrkPredArgs pr{};
+#include "track7_body.h"
+}
+
+// the motion-prior instances (klt_hip_set_predict): whole-frame pyramids with
+// full level-0 records, exact sums.  Frame j's search starts in image 2 at the
+// feature's position moved by its displacement over frame j-1 (TrkPredArgs:
+// read with the list, written back with it), unless that start's window leaves
+// the coarsest level.  The displacement is known only once the frame's status
+// is, so the residue is taken in place (a.merge_res is ignored) and no corners
+// are carried.  Kernels of their own, like the forward-backward ones, so that
+// every other instance keeps its arguments and stays the code it was; they are
+// instantiated in a code object of their own (track7_pred.hip).
+template <bool AOS, int NL>
+__global__ __launch_bounds__(kBlock) void k_track7_pred(TrkArgs a, TrkFramesArgs b, TrkPredArgs pr,
+                                                        float *__restrict__ fx, float *__restrict__ fy,
+                                                        int *__restrict__ fv, int n) {
+  __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
+  constexpr bool BAND = false, FAST = false, FB = false, LAZY = false, HOOK = false, MULTI = false, PRED = true;
+  const TrkFbArgs fb{};
+  const TrkMultiArgs ms{};
 #include "track7_body.h"
 }
 
@@ -937,6 +965,23 @@ static int oob_threshold(int n) {
   return hi;
 }
 
+#if KLT_T7_PRED_UNIT
+// a: launch_track7's, with the bounds thresholds set
+hipError_t launch_track7_pred(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkPredArgs &pr, float *x,
+                              float *y, int *v, int n, int grid, bool two, const char **name) {
+  if (name)
+    *name = a.aos && two ? "kltdev::k_track7_pred<true, 2>"
+            : a.aos      ? "kltdev::k_track7_pred<true, 0>"
+                         : "kltdev::k_track7_pred<false, 0>";
+  if (a.aos && two)
+    hipLaunchKernelGGL((k_track7_pred<true, 2>), dim3(grid), dim3(kBlock), 0, st, a, b, pr, x, y, v, n);
+  else if (a.aos)
+    hipLaunchKernelGGL((k_track7_pred<true, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, pr, x, y, v, n);
+  else
+    hipLaunchKernelGGL((k_track7_pred<false, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, pr, x, y, v, n);
+  return hipGetLastError();
+}
+#else
 hipError_t launch_track7_multi(hipStream_t st, const TrkArgs &a_in, const TrkFramesArgs &b, const TrkMultiArgs &m,
                                float *x, float *y, int *v, int n, const char **name) {
   // the runtime sends interleaved full-record levels of one size in A and B,
@@ -958,7 +1003,7 @@ hipError_t launch_track7_multi(hipStream_t st, const TrkArgs &a_in, const TrkFra
 }
 
 hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const TrkFramesArgs &b, float *x, float *y,
-                         int *v, int n, const char **name, const TrkFbArgs *fb) {
+                         int *v, int n, const char **name, const TrkFbArgs *fb, const TrkPredArgs *pr) {
   TrkArgs a = a_in;
   for (int l = 0; l < KLT_HIP_MAX_LEVELS; ++l) {
     a.oobx[l] = oob_threshold(a.B[l].w);
@@ -970,7 +1015,7 @@ hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const T
   // (interleaved levels are the fused path's, always two levels deep)
   const bool two = KLT_T7_NL2 && a.nlev == 2;
   if (fb) {  // the runtime refuses band calls and fast sums with the check on
-    if (band || a.fast) return hipErrorInvalidValue;
+    if (band || a.fast || pr) return hipErrorInvalidValue;
     if (name)
       *name = a.aos && two ? "kltdev::k_track7_fb<true, 2>"
               : a.aos      ? "kltdev::k_track7_fb<true, 0>"
@@ -982,6 +1027,10 @@ hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const T
     else
       hipLaunchKernelGGL((k_track7_fb<false, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, *fb, x, y, v, n);
     return hipGetLastError();
+  }
+  if (pr) {  // the runtime refuses band calls, fast sums, lazy gradients and the checks with the prior on
+    if (band || a.fast || a.lazy || !pr->vx || !pr->vy) return hipErrorInvalidValue;
+    return launch_track7_pred(st, a, b, *pr, x, y, v, n, grid, two, name);
   }
   if (a.lazy) {  // the runtime sends whole-frame interleaved pyramids here (fast sums: two levels)
     if (band || !a.aos || (a.fast && !two)) return hipErrorInvalidValue;
@@ -1043,5 +1092,6 @@ hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const T
     hipLaunchKernelGGL((k_track7<false, false, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y, v, n);
   return hipGetLastError();
 }
+#endif  // KLT_T7_PRED_UNIT
 
 }  // namespace kltdev

@@ -2,9 +2,9 @@
 // included inside each kernel: the FB-off kernels keep their by-value
 // arguments and compile to what they were before the forward-backward
 // instances existed.  The including kernel provides: the template parameters
-// BAND, AOS, NL, FAST, LAZY, HOOK; constexpr bool FB, MULTI; TrkArgs a;
-// TrkFramesArgs b; TrkFbArgs fb; TrkMultiArgs ms; fx, fy, fv, n; and the LDS
-// array red_all.  The lazy-gradient instances run at their scalar register
+// BAND, AOS, NL, FAST, LAZY, HOOK; constexpr bool FB, MULTI, PRED; TrkArgs a;
+// TrkFramesArgs b; TrkFbArgs fb; TrkMultiArgs ms; TrkPredArgs pr; fx, fy, fv,
+// n; and the LDS array red_all.  The lazy-gradient instances run at their scalar register
 // limit; what LATE, ROLL and the pinned lane numbers below do for them keeps
 // spilled scalars and argument loads out of their frame loop (DESIGN section 4,
 // "Scalar spills off the lazy tracker's chain").  Every other instance
@@ -12,6 +12,7 @@
   // LATE: what only a leaving wave needs is read from the argument segment
   // there (track7.hip's T7KArgs: the arguments of k_track7 / k_track7_hook)
   constexpr bool LATE = LAZY && !FB && !MULTI;
+  static_assert(!PRED || (!FB && !MULTI && !LAZY && !BAND && !FAST && !HOOK), "k_track7_pred: full records, exact sums");
   static_assert(!HOOK || LATE, "wave_exit reads T7KArgs");
   if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -58,7 +59,11 @@
   float x = u(fx[f]), y = u(fy[f]);
   int v = u(fv[f]);
   const int nlev = NL > 0 ? NL : a.nlev;
-  const bool merge = !FB && a.merge_res && nlev >= 2;
+  const bool merge = !FB && !PRED && a.merge_res && nlev >= 2;
+  // PRED (klt_hip_set_predict): the feature's last displacement, wave-uniform
+  // over the frames; loaded with the list, stored with it by lane 0
+  float pvx = 0.0f, pvy = 0.0f;
+  if constexpr (PRED) pvx = u(pr.vx[f]), pvy = u(pr.vy[f]);
   Pending pd;
   Counts cnt;
   Carry carry;  // lazy-gradient instances: the last level-0 pass's image-2 corners (unused otherwise)
@@ -82,6 +87,8 @@
     const bool job = pd.on;  // frame j-1 is tentatively tracked at (x, y)
     const float xp = x, yp = y;
     int rstat = kTracked;
+    if constexpr (PRED)
+      if (v != 0) pvx = 0.0f, pvy = 0.0f;  // lost, or fresh from selection or replacement: no prior
     if (v >= 0 || job) {
       // one frame of KLTTrackFeatures for this feature (:1348-1437)
       const Lev R = lev_img1<MULTI, ROLL>(a, b, 0, j, sq, nsq, pimg[0], pil);
@@ -96,6 +103,15 @@
         yl = u(a.ss_inv != 0.0f ? yl * a.ss_inv : yl / a.ss);
       }
       float xo = xl, yo = yl;
+      if constexpr (PRED) {  // image 2's start: the position moved by the last displacement, scaled like xl
+        xo = u(x + pvx);
+        yo = u(y + pvy);
+#pragma unroll
+        for (int r = nlev - 1; r >= 0; --r) {
+          xo = u(a.ss_inv != 0.0f ? xo * a.ss_inv : xo / a.ss);
+          yo = u(a.ss_inv != 0.0f ? yo * a.ss_inv : yo / a.ss);
+        }
+      }
       int val = kTracked;
       bool lost_prev = false;
 #pragma unroll
@@ -106,6 +122,12 @@
         yo = u(yo * a.ss);
         const Lev LA = lev_img1<MULTI, ROLL>(a, b, r, j, sq, nsq, pimg[ROLL ? r : 0], pil);
         const Lev LB = lev_cur<MULTI>(a, b, r, j, sq, nsq);
+        if constexpr (PRED)  // a start whose window is not inside the coarsest level (NaN included): unpredicted
+          if (r == nlev - 1) {
+            const bool in = !out7(xo, yo, LB.tx, LB.ty);
+            xo = u(in ? xo : xl);
+            yo = u(in ? yo : yl);
+          }
         const bool lj = job && r == nlev - 1;
         T7_T(t_l0);
         if (LAZY && r == 0)
@@ -136,6 +158,14 @@
           y = yo;
           v = kTracked;
         }
+      }
+    }
+    if constexpr (PRED) {  // two float subtractions; a lost feature keeps no motion
+      pvx = v == kTracked ? u(x - xp) : 0.0f;
+      pvy = v == kTracked ? u(y - yp) : 0.0f;
+      if (pr.tvx && lane == 0) {
+        pr.tvx[j * pr.tstride + f] = pvx;
+        pr.tvy[j * pr.tstride + f] = pvy;
       }
     }
     if constexpr (FB) {
@@ -231,6 +261,10 @@
     ox[f] = x;
     oy[f] = y;
     ov[f] = v;
+    if constexpr (PRED) {
+      pr.vx[f] = pvx;
+      pr.vy[f] = pvy;
+    }
     if (count) {
       const int k = slot & (kCountSlots - 1);
       atomicAdd(&count[k], (unsigned long long)cnt.solves);

@@ -112,6 +112,9 @@ DEVICE_PROTOS = {
     "klt_hip_set_fb": (C.c_int, [V, C.c_int, C.c_float]),
     "klt_hip_get_fb": (C.c_int, [V, IP, FP]),
     "klt_hip_set_fb_table": (C.c_int, [V, V, C.c_long]),
+    "klt_hip_set_predict": (C.c_int, [V, C.c_int, V, V]),
+    "klt_hip_get_predict": (C.c_int, [V, IP, C.POINTER(V), C.POINTER(V)]),
+    "klt_hip_set_predict_table": (C.c_int, [V, V, V, C.c_long]),
     "klt_hip_set_frames_affine": (C.c_int, [V, C.POINTER(AffineDesc), V, V]),
     "klt_hip_get_frames_affine": (C.c_int, [V, IP]),
     "klt_hip_set_affine_table": (C.c_int, [V, V, V, C.c_long]),
@@ -223,6 +226,7 @@ DEVICE_PROTOS = {
     "klt_amd_track_desc": (None, [V, C.POINTER(TrackDesc)]),
     "klt_amd_set_reduction": (None, [V, C.c_int]),
     "klt_amd_set_fb_check": (C.c_int, [V, C.c_int, C.c_float]),
+    "klt_amd_set_prediction": (C.c_int, [V, C.c_int]),
     "klt_amd_release_cached_devices": (C.c_int, []),
     "klt_amd_register_buffer": (C.c_int, [V, V, C.c_size_t]),
     "klt_amd_unregister_buffer": (C.c_int, [V, V]),
