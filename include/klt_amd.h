@@ -64,6 +64,27 @@ int klt_amd_set_fb_check(KLT_TrackingContext tc, int on, float max_dist);
    lighting_insensitive (the device call's refusal).  Returns 0. */
 int klt_amd_set_prediction(KLT_TrackingContext tc, int on);
 
+/* Region mask (klt_hip_set_mask in klt_hip.h has the exact definition): one
+   byte per pixel, ncols x nrows, rows ncols bytes apart, nonzero = allowed,
+   zero = masked; flags is an OR of KLT_HIP_MASK_SELECT and KLT_HIP_MASK_TRACK.
+   The mask is copied into device memory that the tracking context owns, freed
+   with it or with the next klt_amd_set_mask; NULL (or flags 0) clears it.
+   With KLT_HIP_MASK_SELECT, KLTSelectGoodFeatures, KLTReplaceLostFeatures,
+   KLTTrackSequenceReplace and KLTTrackSequencesReplace never place a feature
+   on a masked pixel.  With KLT_HIP_MASK_TRACK, KLTTrackFeatures,
+   KLTTrackSequence and KLTTrackSequenceReplace (which stay on their batched
+   path), in sequential mode or not, lose a feature whose new position lies on a
+   masked pixel: x = y = -1, val = KLT_AMD_MASKED.  KLTTrackSequences* run their
+   per-sequence loop with the tracking use on.  A call whose image is not
+   ncols x nrows is a KLTError while a mask is set; so is a tracking call with
+   the tracking use on and klt_amd_set_fb_check, klt_amd_set_prediction,
+   affineConsistencyCheck >= 0 or KLT_HIP_FAST sums, or with a window other than
+   7x7 or lighting_insensitive (the device call's refusal).  Returns 0, or -1
+   with a KLTWarning and the setting unchanged for flags outside the two bits,
+   an empty size, or a failed device copy. */
+#define KLT_AMD_MASKED -7
+int klt_amd_set_mask(KLT_TrackingContext tc, const unsigned char *host_mask, int ncols, int nrows, int flags);
+
 /* The reference harness loop (example3.c:54-74 without REPLACE) in one call:
      for (i = 1; i < nframes; i++) {
        KLTTrackFeatures(tc, frames[i-1], frames[i], ncols, nrows, fl);

@@ -285,6 +285,65 @@ int klt_hip_get_predict(klt_hip_ctx *ctx, int *on, float **dev_vx, float **dev_v
    counted as klt_hip_set_fb_table's.  Both or neither; NULL clears them, and
    so does klt_hip_ctx_reset. */
 int klt_hip_set_predict_table(klt_hip_ctx *ctx, float *dev_tab_vx, float *dev_tab_vy, long stride);
+/* Region mask: the parts of the image that are not scene (a vehicle hood, the
+   rig's own body, a burnt-in timestamp, a vignetted rim).  dev_mask is device
+   memory, one byte per level-0 pixel, nrows rows `pitch` >= ncols bytes apart;
+   nonzero = allowed, zero = masked (OpenCV's convention).  flags is an OR of
+   the two uses, switched separately:
+     KLT_HIP_MASK_SELECT  selection and replacement never place a feature on a
+       masked pixel.  The walk of _KLTSelectGoodFeatures /
+       KLTReplaceLostFeatures is the reference's, with every masked pixel
+       marked in its feature map before the first point is visited (when
+       replacing: in addition to the squares of the live features).  The point
+       list and its sort are those of the whole map, so the order, ties
+       included, is unchanged and an all-allowed mask gives the bytes of no
+       mask; slots that cannot be filled become (-1, -1, KLT_NOT_FOUND) and
+       `changed` keeps its meaning.  Honoured wherever the selection engine
+       runs: klt_hip_select, klt_hip_select_dev_map, klt_hip_select_map, the
+       replacement inside klt_hip_track_frames / _host
+       (klt_hip_set_frames_replace) and klt_hip_track_frames_multi_replace (one
+       mask for every sequence), and the sharded replacement (each rank's
+       context carries its mask).  It composes with every tracker
+       configuration and never refuses anything.
+     KLT_HIP_MASK_TRACK  a tracked feature whose new position lies on a masked
+       pixel is lost.  One frame of KLTTrackFeatures gives a status val and a
+       position (xo, yo); after the level loop the status becomes KLT_OOB if
+       val is KLT_OOB or the border test fails (unchanged, and first);
+       otherwise KLT_HIP_MASKED with x = y = -1 if val != KLT_SMALL_DET and
+       mask[(int)yo * pitch + (int)xo] == 0; otherwise val.  Like the border
+       test it is a test of position: it beats KLT_LARGE_RESIDUE and
+       KLT_MAX_ITERATIONS (every level ran, the position is a level-0 one) and
+       not KLT_SMALL_DET (the loop broke at a coarser level).  A feature that
+       starts on a masked pixel is tracked and tested like any other; a masked
+       feature is lost from that frame on, and a replacement inside the call
+       refills its slot.  Honoured by klt_hip_track with device arrays,
+       klt_hip_track_sequence, klt_hip_track_frames and
+       klt_hip_track_frames_host, with or without klt_hip_set_frames_replace:
+       the 7x7 window with KLT_HIP_EXACT sums on fused or generic pyramids of
+       any depth.  The batched calls whose banks hold level 0 as the image
+       plane alone (klt_hip_set_lazy_grad 1) run the k_track7_mask_lazy
+       instances, which keep the lazy gradients and the deferred residue
+       (klt_hip_set_track_merge): the tentative position is tested at once and
+       a pending residue verdict is dropped.  Every other honoured call runs
+       the k_track7_mask instances on full level-0 records with the residue
+       taken in place.  Results do not depend on either setting, on the track
+       order, the chunk, or how frames are split over calls.
+       Refused with -1 and a message before any launch,
+       lists untouched, while this bit is on: the forward-backward check, the
+       affine check (inside the launch and klt_hip_track_affine), the motion
+       prior, KLT_HIP_FAST sums, any other window, lighting-insensitive mode
+       and the generic tracker, klt_hip_track_frames_band and the sharded
+       drivers, the multi-sequence calls (klt_hip_multi_covers returns -1 as
+       well), klt_hip_track with host arrays.
+   NULL or flags 0 clears the setting, and so does klt_hip_ctx_reset.  Flags
+   outside the two bits return -1 with the setting unchanged.  The caller keeps
+   the memory valid while the mask is set.  A pitch below the image width is
+   refused by the calls that learn the width, before any launch. */
+#define KLT_HIP_MASKED (-7)
+#define KLT_HIP_MASK_SELECT 1
+#define KLT_HIP_MASK_TRACK 2
+int klt_hip_set_mask(klt_hip_ctx *ctx, const unsigned char *dev_mask, long pitch, int flags);
+int klt_hip_get_mask(klt_hip_ctx *ctx, const unsigned char **dev_mask, long *pitch, int *flags);
 /* tuning hook: 1 (default) raises the tracker waves' issue priority
    (s_setprio 3) so that, when the next chunk's pyramids are built beside the
    tracker (overlapped schedule, band calls with build-ahead), a feature's

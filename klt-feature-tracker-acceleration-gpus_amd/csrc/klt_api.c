@@ -55,6 +55,10 @@ typedef struct {
      zero when the setting is turned on or the list size changes */
   int pred_on, pred_n;
   float *pred_vx, *pred_vy;
+  /* region mask (klt_amd_set_mask): a device copy of mask_w x mask_h bytes that
+     this record owns (a fresh_copy borrows it) and the uses switched on */
+  unsigned char *mask_dev;
+  int mask_w, mask_h, mask_flags, mask_borrowed;
   /* affine consistency check: the feature list whose stored windows the
      device store holds, and per slot the aff_img whose data it holds */
   KLT_FeatureList aff_list;
@@ -182,6 +186,45 @@ static int apply_pred(KLT_TrackingContext tc, const char *who)
     KLTError("(%s) the motion prior needs exact sums (KLT_HIP_EXACT)", who);
   dev_check(tc, klt_hip_set_predict(device_of(tc), 0, NULL, NULL), "motion prior setting");
   return f->pred_on && tc->sequentialMode;
+}
+
+/* The region mask of this tracking context onto its device context, before
+   every selection and tracking call.  A call whose image is not the mask's size
+   is an error, and so are the combinations the tracking use does not cover, as
+   the motion prior's are.  Returns 1 when the call tracks with the mask's
+   tracking use on: its lists then go to the device call in device memory. */
+static int apply_mask(KLT_TrackingContext tc, const char *who, int ncols, int nrows, int tracking)
+{
+  klt_ctx_full *f = FULL(tc);
+  const int track = tracking && f->mask_dev && (f->mask_flags & KLT_HIP_MASK_TRACK);
+  if (f->mask_dev && (f->mask_w != ncols || f->mask_h != nrows))
+    KLTError("(%s) the region mask is %d by %d, the image %d by %d (klt_amd_set_mask)", who, f->mask_w, f->mask_h, ncols,
+             nrows);
+  if (track && f->fb_on) KLTError("(%s) the region mask's tracking use does not combine with the forward-backward check", who);
+  if (track && tc->affineConsistencyCheck >= 0)
+    KLTError("(%s) the region mask's tracking use does not combine with affineConsistencyCheck=%d", who,
+             tc->affineConsistencyCheck);
+  if (track && f->pred_on) KLTError("(%s) the region mask's tracking use does not combine with the motion prior", who);
+  if (track && f->reduction != KLT_HIP_EXACT)
+    KLTError("(%s) the region mask's tracking use needs exact sums (KLT_HIP_EXACT)", who);
+  dev_check(tc,
+            klt_hip_set_mask(device_of(tc), f->mask_dev, f->mask_w,
+                             tracking ? f->mask_flags : f->mask_flags & KLT_HIP_MASK_SELECT),
+            "region mask setting");
+  return track;
+}
+
+/* the mask's device copy goes with the record (or with the next mask): nothing
+   queued on the device context reads it any more, and the context forgets it */
+static void mask_drop(klt_ctx_full *f)
+{
+  if (f->mask_dev && f->dev) {
+    klt_hip_sync(f->dev);
+    klt_hip_set_mask(f->dev, NULL, 0, 0);
+    if (!f->mask_borrowed) klt_hip_free(f->dev, f->mask_dev);
+  }
+  f->mask_dev = NULL;
+  f->mask_w = f->mask_h = f->mask_flags = f->mask_borrowed = 0;
 }
 
 /* the state arrays for a list of n slots: kept from call to call, zeroed when n changes */
@@ -422,6 +465,7 @@ EXPORT void KLTFreeTrackingContext(KLT_TrackingContext tc)
   klt_ctx_full *f;
   if (!tc) return;
   f = FULL(tc);
+  mask_drop(f);
   release_device(f->dev);
   free(f->aff_owner);
   pred_drop(f);
@@ -664,6 +708,7 @@ static void select_features(KLT_TrackingContext tc, KLT_PixelType *img, int ncol
 
   window_fix(tc, NULL);
   dev = device_of(tc);
+  apply_mask(tc, replacing ? "KLTReplaceLostFeatures" : "KLTSelectGoodFeatures", ncols, nrows, 0);
   if (replacing && tc->sequentialMode && tc->pyramid_last != NULL && f->last_slot >= 0) {
     slot = f->last_slot; /* level 0 of the last pyramid (:342-348) */
   } else {
@@ -932,7 +977,7 @@ EXPORT void KLTTrackFeatures(KLT_TrackingContext tc, KLT_PixelType *img1, KLT_Pi
   klt_hip_ctx *dev;
   klt_hip_pyr_desc d;
   klt_hip_track_desc td;
-  int slot1, slot2, k, pred, n = fl->nFeatures;
+  int slot1, slot2, k, pred, mtrack, n = fl->nFeatures;
   float *x, *y;
   int *v;
 
@@ -947,6 +992,7 @@ EXPORT void KLTTrackFeatures(KLT_TrackingContext tc, KLT_PixelType *img1, KLT_Pi
   apply_fb(tc, "KLTTrackFeatures");
   pred = apply_pred(tc, "KLTTrackFeatures");
   if (FULL(tc)->pred_on && !pred) pred_drop(FULL(tc)); /* not sequential: no frame before this one */
+  mtrack = apply_mask(tc, "KLTTrackFeatures", ncols, nrows, 1);
 
   if (tc->sequentialMode && tc->pyramid_last != NULL && f->last_slot >= 0) {
     if (f->last_w != ncols || f->last_h != nrows)
@@ -1015,6 +1061,20 @@ EXPORT void KLTTrackFeatures(KLT_TrackingContext tc, KLT_PixelType *img1, KLT_Pi
              klt_hip_memcpy(dev, v, d + 2 * (size_t)n, nb, MEMCPY_D2H) ||
              klt_hip_memcpy(dev, f->pred_vx, d + 3 * (size_t)n, nb, MEMCPY_D2H) ||
              klt_hip_memcpy(dev, f->pred_vy, d + 4 * (size_t)n, nb, MEMCPY_D2H);
+      dev_check(tc, rc, "feature tracking");
+      klt_hip_free(dev, d);
+    } else if (mtrack && n > 0) {
+      /* the mask's kernels take the list in device memory */
+      const size_t nb = sizeof(float) * (size_t)n;
+      float *d = (float *)klt_hip_malloc(dev, 3 * nb);
+      int rc;
+      if (!d) KLTError("(KLTTrackFeatures) device memory for the masked list: %s", klt_hip_last_error(dev));
+      rc = klt_hip_memcpy(dev, d, x, nb, MEMCPY_H2D) || klt_hip_memcpy(dev, d + n, y, nb, MEMCPY_H2D) ||
+           klt_hip_memcpy(dev, d + 2 * (size_t)n, v, nb, MEMCPY_H2D);
+      if (!rc) rc = klt_hip_track(dev, slot1, slot2, &td, d, d + n, (int *)(d + 2 * (size_t)n), n, 1);
+      if (!rc)
+        rc = klt_hip_memcpy(dev, x, d, nb, MEMCPY_D2H) || klt_hip_memcpy(dev, y, d + n, nb, MEMCPY_D2H) ||
+             klt_hip_memcpy(dev, v, d + 2 * (size_t)n, nb, MEMCPY_D2H);
       dev_check(tc, rc, "feature tracking");
       klt_hip_free(dev, d);
     } else {
@@ -1117,6 +1177,7 @@ static void track_sequence(KLT_TrackingContext tc, KLT_PixelType **frames, int n
   dev = device_of(tc);
   apply_fb(tc, every ? "KLTTrackSequenceReplace" : "KLTTrackSequence");
   pred = apply_pred(tc, every ? "KLTTrackSequenceReplace" : "KLTTrackSequence");
+  apply_mask(tc, every ? "KLTTrackSequenceReplace" : "KLTTrackSequence", ncols, nrows, 1);
   seq_start = tc->sequentialMode && tc->pyramid_last != NULL && f->last_slot >= 0;
   if (seq_start && (f->last_w != ncols || f->last_h != nrows))
     KLTError("(KLTTrackSequence) Size of incoming image (%d by %d) is different from size of "
@@ -1320,6 +1381,11 @@ static KLT_TrackingContext fresh_copy(KLT_TrackingContext tc)
   g->fb_on = FULL(tc)->fb_on;
   g->fb_dist = FULL(tc)->fb_dist;
   g->pred_on = FULL(tc)->pred_on; /* its state starts at zero */
+  g->mask_dev = FULL(tc)->mask_dev; /* tc's own device copy, which outlives the copy of tc */
+  g->mask_w = FULL(tc)->mask_w;
+  g->mask_h = FULL(tc)->mask_h;
+  g->mask_flags = FULL(tc)->mask_flags;
+  g->mask_borrowed = 1;
   return t;
 }
 
@@ -1388,6 +1454,8 @@ static void track_sequences(KLT_TrackingContext tc, KLT_PixelType ***frames, int
   if (multi) {
     dev = device_of(tc);
     apply_fb(tc, every ? "KLTTrackSequencesReplace" : "KLTTrackSequences");
+    /* with the mask's tracking use on, the multi call does not cover it: the loop below */
+    apply_mask(tc, every ? "KLTTrackSequencesReplace" : "KLTTrackSequences", ncols, nrows, 1);
     klt_amd_track_desc(tc, &td);
     multi = klt_hip_multi_covers(dev, &D, &td) == 1;
   }
@@ -1611,6 +1679,38 @@ EXPORT int klt_amd_set_prediction(KLT_TrackingContext tc, int on)
 {
   FULL(tc)->pred_on = on ? 1 : 0;
   pred_drop(FULL(tc)); /* the state starts at zero (pred_state) */
+  return 0;
+}
+
+EXPORT int klt_amd_set_mask(KLT_TrackingContext tc, const unsigned char *host_mask, int ncols, int nrows, int flags)
+{
+  klt_ctx_full *f = FULL(tc);
+  klt_hip_ctx *dev;
+  unsigned char *d;
+  if (flags & ~(KLT_HIP_MASK_SELECT | KLT_HIP_MASK_TRACK)) {
+    KLTWarning("(klt_amd_set_mask) flags %d: expected an OR of KLT_HIP_MASK_SELECT and KLT_HIP_MASK_TRACK", flags);
+    return -1;
+  }
+  if (host_mask && flags && (ncols < 1 || nrows < 1)) {
+    KLTWarning("(klt_amd_set_mask) a %d by %d mask", ncols, nrows);
+    return -1;
+  }
+  if (!host_mask || !flags) {
+    mask_drop(f);
+    return 0;
+  }
+  dev = device_of(tc);
+  d = (unsigned char *)klt_hip_malloc(dev, (size_t)ncols * nrows);
+  if (!d || klt_hip_memcpy(dev, d, host_mask, (size_t)ncols * nrows, MEMCPY_H2D)) {
+    KLTWarning("(klt_amd_set_mask) %s", klt_hip_last_error(dev));
+    klt_hip_free(dev, d);
+    return -1;
+  }
+  mask_drop(f); /* the mask before this one */
+  f->mask_dev = d;
+  f->mask_w = ncols;
+  f->mask_h = nrows;
+  f->mask_flags = flags;
   return 0;
 }
 

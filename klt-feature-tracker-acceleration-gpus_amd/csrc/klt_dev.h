@@ -204,6 +204,14 @@ struct TrkPredArgs {
   float *tvx, *tvy;  // optional tables: row j receives the state after frame j; nullptr: none
   long tstride;      // their row stride (elements)
 };
+// region mask, tracking use (klt_hip_set_mask with KLT_HIP_MASK_TRACK): the
+// mask instances of k_track7 take this beside TrkFramesArgs, so the others keep
+// their argument layout
+struct TrkMaskArgs {
+  const unsigned char *mask;  // one byte per level-0 pixel, zero = masked
+  long pitch;                 // bytes between rows
+};
+constexpr int kMasked = KLT_HIP_MASKED;
 // several independent sequences in one launch (klt_hip_track_frames_multi):
 // the multi instances take this beside TrkFramesArgs, so the others keep
 // their argument layout.  Sequence s owns features [first[s], first[s + 1]) of
@@ -347,11 +355,15 @@ size_t track_affine_lds_bytes(int mode);
 // track7.hip: the default configuration (7x7 window, exact sums, no gain/bias,
 // one wave per feature) with the latency-lean pass; band: escape checks
 // pr != nullptr: the motion-prior instances (exact sums, whole frames, not together with fb)
+// mk != nullptr: the region-mask instances (the same; not together with fb or pr)
 hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y,
                          int *v, int n, const char **name = nullptr, const TrkFbArgs *fb = nullptr,
-                         const TrkPredArgs *pr = nullptr);
+                         const TrkPredArgs *pr = nullptr, const TrkMaskArgs *mk = nullptr);
 // track7_pred.hip: the k_track7_pred instances, for launch_track7 (a with the bounds thresholds, its grid and depth)
 hipError_t launch_track7_pred(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkPredArgs &pr, float *x,
+                              float *y, int *v, int n, int grid, bool two, const char **name);
+// track7_mask.hip: the k_track7_mask instances, in the same way
+hipError_t launch_track7_mask(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkMaskArgs &mk, float *x,
                               float *y, int *v, int n, int grid, bool two, const char **name);
 // the multi-sequence instances (whole-frame interleaved pyramids, exact sums)
 hipError_t launch_track7_multi(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkMultiArgs &m, float *x,
@@ -422,7 +434,7 @@ int sel_default_threshold();
 void sel_engine_stats(const SelEngine *e, long *downloaded, long *steps, long *visited, double *us);
 int sel_engine_run(SelEngine *e, hipStream_t st, const int *dev_vals, int nx, int ny, int bx, int by, int step,
                    int W, int H, int mindist, int min_eigenvalue, int overwrite_all, float *x, float *y, int *val,
-                   unsigned char *changed, int n, std::string *err);
+                   unsigned char *changed, int n, const uint8_t *mask, long mask_pitch, std::string *err);
 int sel_engine_sort(SelEngine *e, hipStream_t st, const int *dev_vals, int n, int *out_val, int *out_idx,
                     std::string *err);
 hipError_t launch_affine_move(hipStream_t st, int dir, const int *idx, int m, int s3, float *staging, float *store);

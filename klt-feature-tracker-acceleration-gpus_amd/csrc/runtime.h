@@ -184,6 +184,11 @@ struct __attribute__((visibility("default"))) klt_hip_ctx {  // its constructor 
   long pred_stride = 0;
   float *d_pred = nullptr;
   size_t pred_cap = 0;
+  // region mask (klt_hip_set_mask): the caller's device bytes, their row
+  // pitch and the uses switched on (KLT_HIP_MASK_*); null / 0: none
+  const unsigned char *mask = nullptr;
+  long mask_pitch = 0;
+  int mask_flags = 0;
   // affine check inside the tracker launch (klt_hip_set_frames_affine): the
   // caller's device arrays, the optional tables (klt_hip_set_affine_table);
   // aff_fresh: the next tracker launch is the first of its API call (windows
@@ -454,6 +459,18 @@ struct TailRelease {
   unsigned thr;
 };
 
+// the region mask as the selection engine takes it (null unless the selection
+// bit is on), and the check of the calls that learn the image width: a mask
+// whose rows are shorter than the image's is refused before any launch
+inline const unsigned char *sel_mask(const klt_hip_ctx *c) {
+  return (c->mask_flags & KLT_HIP_MASK_SELECT) ? c->mask : nullptr;
+}
+inline bool mask_tracks(const klt_hip_ctx *c) { return (c->mask_flags & KLT_HIP_MASK_TRACK) != 0; }
+inline int mask_refused(klt_hip_ctx *c, int ncols, const char *who) {
+  if (!c->mask_flags || c->mask_pitch >= ncols) return 0;
+  return fail(c, "%s: region mask pitch %ld < image width %d (klt_hip_set_mask)", who, c->mask_pitch, ncols);
+}
+
 // runtime.hip
 int ensure_pipeline(klt_hip_ctx *c);
 // runtime_pyr.hip
@@ -481,6 +498,7 @@ int order_features(klt_hip_ctx *c, hipStream_t st, int nrows, const float *y, co
 int fb_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const char *who);
 int aff_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, int n, const char *who);
 int pred_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const char *who);
+int mask_track_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const char *who);
 int track_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, int n, const char *who);
 int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc *d, const TrkArgs &a,
                         const TrkFramesArgs &b, float *x, float *y, int *v, int n, const float *own = nullptr,

@@ -314,6 +314,9 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->track_kernel = nullptr;  // klt_hip_track_kernel: "" before the next owner's first launch
   c->fb_on = 0;
   c->fb_dist = 0.0f;
+  c->mask = nullptr;
+  c->mask_pitch = 0;
+  c->mask_flags = 0;
   c->fb_tab = nullptr;
   c->fb_stride = 0;
   c->pred_on = 0;
@@ -684,6 +687,26 @@ KLT_API int klt_hip_set_predict_table(klt_hip_ctx *c, float *dev_tab_vx, float *
   return 0;
 }
 
+KLT_API int klt_hip_set_mask(klt_hip_ctx *c, const unsigned char *dev_mask, long pitch, int flags) {
+  if (!c) return fail(c, "set_mask: null context");
+  if (flags & ~(KLT_HIP_MASK_SELECT | KLT_HIP_MASK_TRACK))
+    return fail(c, "set_mask: flags %#x (KLT_HIP_MASK_SELECT | KLT_HIP_MASK_TRACK)", (unsigned)flags);
+  if (dev_mask && flags && pitch < 1) return fail(c, "set_mask: pitch %ld < 1", pitch);
+  const bool on = dev_mask && flags;
+  c->mask = on ? dev_mask : nullptr;
+  c->mask_pitch = on ? pitch : 0;
+  c->mask_flags = on ? flags : 0;
+  return 0;
+}
+
+KLT_API int klt_hip_get_mask(klt_hip_ctx *c, const unsigned char **dev_mask, long *pitch, int *flags) {
+  if (!c) return fail(c, "get_mask: null context");
+  if (dev_mask) *dev_mask = c->mask;
+  if (pitch) *pitch = c->mask_pitch;
+  if (flags) *flags = c->mask_flags;
+  return 0;
+}
+
 KLT_API int klt_hip_set_track_count(klt_hip_ctx *c, int on) {
   if (!c) return fail(c, "set_track_count: null context");
   if (use_device(c)) return -1;
@@ -783,12 +806,14 @@ KLT_API int klt_hip_select(klt_hip_ctx *c, int s, const klt_hip_select_desc *d, 
   if (s < 0 || s >= KLT_HIP_MAX_SLOTS || c->slot[s].nlev < 1) return fail(c, "select: bad slot");
   if (c->slot[s].lv[0].w != ncols || c->slot[s].lv[0].h != nrows)
     return fail(c, "select: slot %d is %dx%d, image %dx%d", s, c->slot[s].lv[0].w, c->slot[s].lv[0].h, ncols, nrows);
+  if (mask_refused(c, ncols, "select")) return -1;
   if (use_device(c)) return -1;
   int nx = 0, ny = 0;
   if (eigen_to_dev(c, s, d, &nx, &ny)) return -1;
   std::string e;
   if (sel_engine_run(sel_of(c), c->stream, c->d_eig, nx, ny, d->borderx, d->bordery, d->nSkippedPixels + 1, ncols,
-                     nrows, mindist < 0 ? 0 : mindist, min_eigenvalue, overwrite_all, x, y, val, changed, n, &e))
+                     nrows, mindist < 0 ? 0 : mindist, min_eigenvalue, overwrite_all, x, y, val, changed, n, sel_mask(c),
+                     c->mask_pitch, &e))
     return fail(c, "select: %s", e.c_str());
   return 0;
 }
@@ -799,10 +824,12 @@ KLT_API int klt_hip_select_dev_map(klt_hip_ctx *c, const int *dev_map, int nx, i
                                    unsigned char *changed, int n) {
   if (!c || !d || (nx * ny > 0 && !dev_map) || (n > 0 && (!x || !y || !val || !changed)))
     return fail(c, "select_dev_map: null argument");
+  if (mask_refused(c, ncols, "select_dev_map")) return -1;
   if (use_device(c)) return -1;
   std::string e;
   if (sel_engine_run(sel_of(c), c->stream, dev_map, nx, ny, d->borderx, d->bordery, d->nSkippedPixels + 1, ncols,
-                     nrows, mindist < 0 ? 0 : mindist, min_eigenvalue, overwrite_all, x, y, val, changed, n, &e))
+                     nrows, mindist < 0 ? 0 : mindist, min_eigenvalue, overwrite_all, x, y, val, changed, n, sel_mask(c),
+                     c->mask_pitch, &e))
     return fail(c, "select: %s", e.c_str());
   return 0;
 }

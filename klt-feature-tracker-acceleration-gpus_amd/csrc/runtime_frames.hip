@@ -296,6 +296,7 @@ int frames_check(klt_hip_ctx *c, const FramesCall &q, int chunk) {
     return fail(c, "track_frames: the affine check does not combine with the replacement of lost features "
                 "(klt_hip_set_frames_affine, klt_hip_set_frames_replace)");
   if (track_refused(c, q.td, q.band != nullptr, n, q.band ? "track_frames_band" : "track_frames")) return -1;
+  if (mask_refused(c, pd->ncols, q.band ? "track_frames_band" : "track_frames")) return -1;
   const TrkLevel p0 = prev_level(c, 0);
   const int nl = c->prev.bank < 0 ? c->slot[c->prev.slot].nlev : c->bank[c->prev.bank].nlev;
   if (p0.w != pd->ncols || p0.h != pd->nrows || nl != pd->nlevels)
@@ -327,7 +328,8 @@ FramesPlan plan_layout(klt_hip_ctx *c, const FramesCall &q) {
   // level 0 of the banks as the img plane alone, its gradients computed by the
   // tracker for the windows it reads (klt_hip_set_lazy_grad): whole-frame fused
   // pyramids tracked by k_track7 (its fast-sum instance: two levels) without
-  // the forward-backward check or the motion prior, from a previous pyramid that is interleaved
+  // the forward-backward check or the motion prior (the region mask's tracking
+  // use has lazy instances: exact sums only, which it insists on), from a previous pyramid that is interleaved
   // or image-only itself.  Any other call first makes an image-only previous
   // pyramid whole.
   p.lazy = c->lazy_grad && p.fz && t7 && !band && !c->fb_on && !c->aff_on && !c->pred_on &&
@@ -883,6 +885,7 @@ KLT_API int klt_hip_track_frames_host(klt_hip_ctx *c, const klt_hip_pyr_desc *pd
   if (!c || !pd || !td || (nframes > 0 && !frames)) return fail(c, "track_frames_host: null argument");
   if (chunk < 1 || nframes < 0 || n < 0) return fail(c, "track_frames_host: bad nframes/chunk/n");
   const GrayFrames gray_ring(c);  // host frames are gray: so is the upload ring the calls below read
+  if (mask_track_refused(c, td, false, "track_frames_host") || mask_refused(c, pd->ncols, "track_frames_host")) return -1;
   if (pred_refused(c, td, false, "track_frames_host")) return -1;
   if (fb_refused(c, td, false, "track_frames_host")) return -1;
   if (aff_refused(c, td, false, n, "track_frames_host")) return -1;

@@ -30,6 +30,7 @@ int multi_refused(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_trac
   if (c->fb_on) return fail(c, "%s: the forward-backward check is not covered (klt_hip_set_fb)", who);
   if (c->aff_on) return fail(c, "%s: the affine check is not covered (klt_hip_set_frames_affine)", who);
   if (c->pred_on) return fail(c, "%s: the motion prior is not covered (klt_hip_set_predict)", who);
+  if (mask_tracks(c)) return fail(c, "%s: the region mask's tracking use is not covered (klt_hip_set_mask)", who);
   if (td->reduction != KLT_HIP_EXACT) return fail(c, "%s: needs KLT_HIP_EXACT sums", who);
   if (td->window_width != 7 || td->window_height != 7)
     return fail(c, "%s: window %dx%d is not covered (7x7 only)", who, td->window_width, td->window_height);
@@ -169,6 +170,7 @@ int track_multi(klt_hip_ctx *c, const char *who, const klt_hip_pyr_desc *pd, con
                       "(klt_hip_set_frames_replace)", who)
                : fail(c, "%s: not covered while lost features are replaced (klt_hip_set_frames_replace)", who);
   if (rep && replace_desc_refused(c, rep->d, who)) return -1;
+  if (mask_refused(c, pd->ncols, who)) return -1;
   if (rep && rep->count0 < 0) return fail(c, "%s: count0 %ld < 0", who, rep->count0);
   if (nseq < 1 || nseq > KLT_HIP_MAX_SEQUENCES)
     return fail(c, "%s: nseq %d is not in 1..%d", who, nseq, KLT_HIP_MAX_SEQUENCES);
@@ -297,6 +299,8 @@ int track_multi(klt_hip_ctx *c, const char *who, const klt_hip_pyr_desc *pd, con
 KLT_API int klt_hip_multi_covers(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_track_desc *td) {
   if (!c || !pd || !td) return fail(c, "multi_covers: null argument");
   if (c->pred_on) return fail(c, "track_frames_multi: the motion prior is not covered (klt_hip_set_predict)");
+  if (mask_tracks(c))
+    return fail(c, "track_frames_multi: the region mask's tracking use is not covered (klt_hip_set_mask)");
   return multi_refused(c, pd, td, "track_frames_multi") ? 0 : 1;
 }
 

@@ -198,11 +198,37 @@ int pred_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const c
   return 0;
 }
 
+// The region mask's tracking use (klt_hip_set_mask, KLT_HIP_MASK_TRACK) has
+// instances of k_track7 for exact sums on whole-frame pyramids, without either
+// check or the motion prior: anything else fails before a launch.  The
+// selection use alone refuses nothing.
+int mask_track_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, const char *who) {
+  if (!mask_tracks(c)) return 0;
+  if (band) return fail(c, "%s: the region mask's tracking use does not cover band calls (klt_hip_set_mask)", who);
+  if (d->reduction != KLT_HIP_EXACT)
+    return fail(c, "%s: the region mask's tracking use needs KLT_HIP_EXACT sums (klt_hip_set_mask)", who);
+  if (c->fb_on)
+    return fail(c, "%s: the forward-backward check does not combine with the region mask's tracking use "
+                "(klt_hip_set_fb, klt_hip_set_mask)", who);
+  if (c->aff_on)
+    return fail(c, "%s: the affine check does not combine with the region mask's tracking use "
+                "(klt_hip_set_frames_affine, klt_hip_set_mask)", who);
+  if (c->pred_on)
+    return fail(c, "%s: the motion prior does not combine with the region mask's tracking use "
+                "(klt_hip_set_predict, klt_hip_set_mask)", who);
+  if (!t7_tracks(c, d))
+    return fail(c, "%s: the region mask's tracking use needs the default tracker kernel: a 7x7 window without "
+                "lighting-insensitive mode (klt_hip_set_mask; klt_hip_set_track_impl 0, klt_hip_set_track_patch 1, no "
+                "klt_hip_set_prof buffer)", who);
+  return 0;
+}
+
 // all of the above, and the tables' rows hold n features:
 // what a tracker launch of n features in the name of `who` refuses.  An entry
 // point that hands its work to another one asks the two above alone and
 // leaves the table to the launch underneath, in that one's name
 int track_refused(klt_hip_ctx *c, const klt_hip_track_desc *d, bool band, int n, const char *who) {
+  if (mask_track_refused(c, d, band, who)) return -1;
   if (pred_refused(c, d, band, who) || fb_refused(c, d, band, who) || aff_refused(c, d, band, n, who)) return -1;
   if (c->fb_on && c->fb_tab && c->fb_stride < n)
     return fail(c, "%s: forward-backward table stride %ld < n %d", who, c->fb_stride, n);
@@ -216,6 +242,7 @@ int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc
                         long fb_row, TailRelease *tail) {
   if (tail) tail->wait = false;
   if (track_refused(c, d, own != nullptr || a.escape != nullptr, n, "track")) return -1;
+  if (mask_tracks(c) && mask_refused(c, a.ncols, "track")) return -1;
   TimedScope ts(c, T_TRACK, st, b.nframes);
   const int npx = d->window_width * d->window_height;
   const bool exact = d->reduction == KLT_HIP_EXACT, li = d->lighting_insensitive != 0;
@@ -275,6 +302,8 @@ int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc
     pr.tstride = c->pred_stride;
   }
   const TrkPredArgs *prp = c->pred_on ? &pr : nullptr;
+  const TrkMaskArgs mk{c->mask, c->mask_pitch};  // track_refused: t7, exact sums, whole frames
+  const TrkMaskArgs *mkp = mask_tracks(c) ? &mk : nullptr;
   if (t7) {
     // the lazy-gradient instances have twins that count and take times
     if (aa.lazy && aa.aos) bb.wave_t = c->wave_t;
@@ -290,7 +319,8 @@ int track_frames_launch(klt_hip_ctx *c, hipStream_t st, const klt_hip_track_desc
       }
     }
     const int rc =
-        launched(c, "k_track7", launch_track7(st, aa.escape != nullptr, aa, b2, x, y, v, n, &c->track_kernel, fbp, prp));
+        launched(c, "k_track7", launch_track7(st, aa.escape != nullptr, aa, b2, x, y, v, n, &c->track_kernel, fbp, prp,
+                                                  mkp));
     if (rc && tail && tail->wait) {  // counted on the host, maybe not on the device: no wait, and re-base next time
       tail->wait = false;
       c->exits_base = kExitsRebase + 1;
@@ -458,6 +488,9 @@ KLT_API int klt_hip_track(klt_hip_ctx *c, int s1, int s2, const klt_hip_track_de
   for (int l = 0; l < A.nlev; ++l)
     if (A.lv[l].w != B.lv[l].w || A.lv[l].h != B.lv[l].h) return fail(c, "track: slot size mismatch");
   if (check_window(c, d)) return -1;
+  if (mask_track_refused(c, d, false, "track") || mask_refused(c, A.lv[0].w, "track")) return -1;
+  if (mask_tracks(c) && !on_device)
+    return fail(c, "track: the region mask's tracking use takes device arrays (on_device = 1; klt_hip_set_mask)");
   if (pred_refused(c, d, false, "track") || fb_refused(c, d, false, "track")) return -1;
   if (c->pred_on && !on_device)
     return fail(c, "track: the motion prior takes device arrays (on_device = 1; klt_hip_set_predict)");
@@ -583,6 +616,9 @@ KLT_API int klt_hip_track_affine(klt_hip_ctx *c, int s1, int s2, const klt_hip_t
                 "(klt_hip_set_frames_affine); turn that off for per-call checks");
   if (c->pred_on)
     return fail(c, "track_affine: the affine check does not combine with the motion prior (klt_hip_set_predict)");
+  if (mask_tracks(c))
+    return fail(c, "track_affine: the affine check does not combine with the region mask's tracking use "
+                "(klt_hip_set_mask)");
   if (n <= 0) return 0;
   if (s1 < 0 || s1 >= KLT_HIP_MAX_SLOTS || s2 < 0 || s2 >= KLT_HIP_MAX_SLOTS)
     return fail(c, "track_affine: bad slot");
@@ -657,6 +693,7 @@ KLT_API int klt_hip_track_sequence(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, c
   if (c->rep_on)
     return fail(c, "track_sequence: not covered while lost features are replaced (klt_hip_set_frames_replace)");
   if (nsteps <= 0) return 0;
+  if (mask_track_refused(c, td, false, "track_sequence") || mask_refused(c, pd->ncols, "track_sequence")) return -1;
   if (pred_refused(c, td, false, "track_sequence") || fb_refused(c, td, false, "track_sequence") ||
       aff_refused(c, td, false, n, "track_sequence"))
     return -1;

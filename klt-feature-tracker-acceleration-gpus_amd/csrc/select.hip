@@ -103,16 +103,24 @@ __device__ __forceinline__ int block_exscan(int v, int *tmp, int &total) {
 }
 
 // kv[i] = {val, i | blocked}: blocked when the grid point lies in a square
-// painted around a live feature (map != null, REPLACE mode)
+// painted around a live feature (map != null, REPLACE mode), or on a masked
+// pixel of the region mask (mask != null, klt_hip_set_mask: one byte per level-0
+// pixel, rows mpitch bytes apart, zero = masked) -- the reference's feature map
+// with every masked pixel marked before the walk's first point
 __global__ __launch_bounds__(kSelThreads) void k_sel_init(const int *__restrict__ vals, int nx, int n, int bx, int by,
-                                                         int step, int W, const uint8_t *__restrict__ map,
+                                                         int step, int W, int H, const uint8_t *__restrict__ map,
+                                                         const uint8_t *__restrict__ mask, long mpitch,
                                                          int2 *__restrict__ kv) {
   const int i = blockIdx.x * kSelThreads + threadIdx.x;
   if (i >= n) return;
   unsigned idx = (unsigned)i;
-  if (map) {
+  if (map || mask) {
     const int iy = i / nx, ix = i - iy * nx;
-    if (map[(size_t)(by + iy * step) * W + bx + ix * step]) idx |= kBlockedBit;
+    const int px = bx + ix * step, py = by + iy * step;
+    if (map && map[(size_t)py * W + px]) idx |= kBlockedBit;
+    // a caller's map (klt_hip_select_dev_map) states its own grid: a point
+    // outside the image has no mask byte and is left to the walk
+    if (mask && px >= 0 && px < W && py >= 0 && py < H && mask[(size_t)py * mpitch + px] == 0) idx |= kBlockedBit;
   }
   kv[i] = make_int2(vals[i], (int)idx);
 }
@@ -795,7 +803,7 @@ void sel_engine_stats(const SelEngine *e, long *downloaded, long *steps, long *v
 }
 
 static int sel_prepare(SelEngine *e, hipStream_t st, const int *dev_vals, int nx, int ny, int bx, int by, int step,
-                       int W, const uint8_t *map, std::string *err) {
+                       int W, int H, const uint8_t *map, const uint8_t *mask, long mpitch, std::string *err) {
   const size_t n = (size_t)nx * ny;
   if (sel_grow(&e->d_kv, &e->kv_cap, n, err)) return -1;
   if (!e->d_state) SELCHK(hipMalloc((void **)&e->d_state, sizeof(SelState)));
@@ -813,7 +821,7 @@ static int sel_prepare(SelEngine *e, hipStream_t st, const int *dev_vals, int nx
   for (double &u : e->us) u = 0.0;
   if (n) {
     hipLaunchKernelGGL(k_sel_init, dim3((unsigned)((n + kSelThreads - 1) / kSelThreads)), dim3(kSelThreads), 0, st,
-                       dev_vals, nx, (int)n, bx, by, step, W, map, e->d_kv);
+                       dev_vals, nx, (int)n, bx, by, step, W, H, map, mask, mpitch, e->d_kv);
     SELCHK(hipGetLastError());
   }
   return 0;
@@ -821,10 +829,12 @@ static int sel_prepare(SelEngine *e, hipStream_t st, const int *dev_vals, int nx
 
 // The selection walk of _KLTSelectGoodFeatures (selectGoodFeatures.c:135-239)
 // over the lazily sorted map: x/y/val are the host feature list (in/out);
-// changed[k] = 1 for slots written (a new feature or NOT_FOUND).
+// changed[k] = 1 for slots written (a new feature or NOT_FOUND).  mask: the
+// region mask on the device (null: none), folded into the blocked bit in both
+// overwrite_all modes; the walk itself is the same.
 int sel_engine_run(SelEngine *e, hipStream_t st, const int *dev_vals, int nx, int ny, int bx, int by, int step,
                    int W, int H, int mindist, int min_eigenvalue, int overwrite_all, float *x, float *y, int *val,
-                   unsigned char *changed, int n, std::string *err) {
+                   unsigned char *changed, int n, const uint8_t *mask, long mask_pitch, std::string *err) {
   const int r = mindist - 1;  // :157
   if (min_eigenvalue < 1) min_eigenvalue = 1;
   for (int k = 0; k < n; ++k) changed[k] = 0;
@@ -865,7 +875,7 @@ int sel_engine_run(SelEngine *e, hipStream_t st, const int *dev_vals, int nx, in
     map = e->d_map;
   }
   const double t_start = now_us();
-  if (sel_prepare(e, st, dev_vals, nx, ny, bx, by, step, W, map, err)) return -1;
+  if (sel_prepare(e, st, dev_vals, nx, ny, bx, by, step, W, H, map, mask, mask_pitch, err)) return -1;
   // no wait here: the whole map's first refinement queues behind the map's
   // preparation, and the walk's first wait covers both (us[0] is host time)
   e->us[0] = now_us() - t_start;
@@ -916,7 +926,7 @@ int sel_engine_run(SelEngine *e, hipStream_t st, const int *dev_vals, int nx, in
 // klt_sort_pairs_full produces it on the host
 int sel_engine_sort(SelEngine *e, hipStream_t st, const int *dev_vals, int n, int *out_val, int *out_idx,
                     std::string *err) {
-  if (sel_prepare(e, st, dev_vals, n, 1, 0, 0, 1, n, nullptr, err)) return -1;
+  if (sel_prepare(e, st, dev_vals, n, 1, 0, 0, 1, n, 1, nullptr, nullptr, 0, err)) return -1;
   LazySort ls{e, st, {}, err};
   ls.stk.push_back(Seg{0, n, false});
   int k = 0;

@@ -737,6 +737,9 @@ KLT_API int klt_shard_track(klt_shard *s, const klt_hip_pyr_desc *pd, const klt_
   int pred_on = 0;
   if (klt_hip_get_predict(s->ctx, &pred_on, nullptr, nullptr) == 0 && pred_on)
     return sfail(s, "shard_track: the motion prior does not cover band calls (klt_hip_set_predict)");
+  int mask_flags = 0;
+  if (klt_hip_get_mask(s->ctx, nullptr, nullptr, &mask_flags) == 0 && (mask_flags & KLT_HIP_MASK_TRACK))
+    return sfail(s, "shard_track: the region mask's tracking use does not cover band calls (klt_hip_set_mask)");
   DeviceGuard guard;
   if (hipSetDevice(klt_hip_ctx_device(s->ctx)) != hipSuccess) return abort_comm(s, "shard_track: device");
   hipStream_t st = (hipStream_t)klt_hip_get_stream(s->ctx);
@@ -831,6 +834,12 @@ KLT_API int klt_hip_select_map(klt_hip_ctx *ctx, int ncols, int nrows, const klt
                                int min_eigenvalue, const int *dev_map, float *x, float *y, int *val, int n) {
   if (!ctx || !sd || !dev_map || ncols < 1 || nrows < 1 || n < 0 || (n > 0 && (!x || !y || !val)))
     return ctx ? kltdev::ctx_fail(ctx, "select_map: bad argument") : -1;
+  {
+    long mpitch = 0;
+    int mflags = 0;
+    if (klt_hip_get_mask(ctx, nullptr, &mpitch, &mflags) == 0 && mflags && mpitch < ncols)
+      return kltdev::ctx_fail(ctx, "select_map: region mask pitch %ld < image width %d (klt_hip_set_mask)", mpitch, ncols);
+  }
   DeviceGuard guard;
   if (hipSetDevice(klt_hip_ctx_device(ctx)) != hipSuccess) return kltdev::ctx_fail(ctx, "select_map: hipSetDevice failed");
   int nx, ny, j0, j1;

@@ -41,6 +41,9 @@
 #ifndef KLT_T7_PRED_UNIT
 #define KLT_T7_PRED_UNIT 0  // 1: included by track7_pred.hip, which holds the k_track7_pred instances alone
 #endif
+#ifndef KLT_T7_MASK_UNIT
+#define KLT_T7_MASK_UNIT 0  // 1: included by track7_mask.hip, which holds the k_track7_mask instances alone
+#endif
 #ifndef KLT_T7_NL2
 #define KLT_T7_NL2 1  // the two-level instances (A/B hook: 0 launches the runtime-depth ones)
 #endif
@@ -527,6 +530,16 @@ typedef const __attribute__((address_space(4))) T7KArgs *T7KArgsPtr;
 __device__ __forceinline__ T7KArgsPtr t7_kargs() {
   return (T7KArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
 }
+// the lazy-gradient mask instances (k_track7_mask_lazy): T7KArgs first, so that
+// everything above reads them as it reads the others, the mask after it
+struct T7MaskKArgs {
+  T7KArgs k;
+  TrkMaskArgs mk;
+};
+typedef const __attribute__((address_space(4))) T7MaskKArgs *T7MaskKArgsPtr;
+__device__ __forceinline__ T7MaskKArgsPtr t7_mask_kargs() {
+  return (T7MaskKArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+}
 // the hook's way out (the HOOK instances are lazy-gradient ones)
 __device__ __forceinline__ void wave_exit(int lane, unsigned k) {
   if (lane != 0) return;
@@ -865,10 +878,11 @@ __global__ __launch_bounds__(kBlock, LAZY && NL == 2 ? 5 : LAZY ? 4 : 1) void k_
                                                    float *__restrict__ fy, int *__restrict__ fv, int n) {
   static_assert(!LAZY || (AOS && !BAND), "lazy gradients: whole-frame interleaved pyramids");
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF + (LAZY ? kPat : 0)];
-  constexpr bool FB = false, HOOK = false, MULTI = false, PRED = false;
+  constexpr bool FB = false, HOOK = false, MULTI = false, PRED = false, MASK = false;
   const TrkFbArgs fb{};
   const TrkMultiArgs ms{};
   const TrkPredArgs pr{};
+  const TrkMaskArgs mk{};
 #include "track7_body.h"
 }
 
@@ -881,10 +895,11 @@ __global__ __launch_bounds__(kBlock, NL == 2 ? 5 : 4) void k_track7_hook(TrkArgs
                                                                           float *__restrict__ fy,
                                                                           int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF + kPat];
-  constexpr bool BAND = false, AOS = true, LAZY = true, FB = false, HOOK = true, MULTI = false, PRED = false;
+  constexpr bool BAND = false, AOS = true, LAZY = true, FB = false, HOOK = true, MULTI = false, PRED = false, MASK = false;
   const TrkFbArgs fb{};
   const TrkMultiArgs ms{};
   const TrkPredArgs pr{};
+  const TrkMaskArgs mk{};
 #include "track7_body.h"
 }
 
@@ -894,9 +909,10 @@ __global__ __launch_bounds__(kBlock) void k_track7_fb(TrkArgs a, TrkFramesArgs b
                                                       float *__restrict__ fx, float *__restrict__ fy,
                                                       int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
-  constexpr bool BAND = false, FAST = false, FB = true, LAZY = false, HOOK = false, MULTI = false, PRED = false;
+  constexpr bool BAND = false, FAST = false, FB = true, LAZY = false, HOOK = false, MULTI = false, PRED = false, MASK = false;
   const TrkMultiArgs ms{};
   const TrkPredArgs pr{};
+  const TrkMaskArgs mk{};
 #include "track7_body.h"
 }
 
@@ -912,9 +928,10 @@ __global__ __launch_bounds__(kBlock) void k_track7_multi(TrkArgs a, TrkFramesArg
                                                          int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
   constexpr bool BAND = false, AOS = true, FAST = false, FB = false, LAZY = false, HOOK = false, MULTI = true,
-                 PRED = false;
+                 PRED = false, MASK = false;
   const TrkFbArgs fb{};
   const TrkPredArgs pr{};
+  const TrkMaskArgs mk{};
 #include "track7_body.h"
 }
 
@@ -932,9 +949,50 @@ __global__ __launch_bounds__(kBlock) void k_track7_pred(TrkArgs a, TrkFramesArgs
                                                         float *__restrict__ fx, float *__restrict__ fy,
                                                         int *__restrict__ fv, int n) {
   __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
-  constexpr bool BAND = false, FAST = false, FB = false, LAZY = false, HOOK = false, MULTI = false, PRED = true;
+  constexpr bool BAND = false, FAST = false, FB = false, LAZY = false, HOOK = false, MULTI = false, PRED = true, MASK = false;
   const TrkFbArgs fb{};
   const TrkMultiArgs ms{};
+  const TrkMaskArgs mk{};
+#include "track7_body.h"
+}
+
+// the region-mask instances (klt_hip_set_mask, KLT_HIP_MASK_TRACK): whole-frame
+// pyramids with full level-0 records, exact sums.  After the level loop a
+// feature whose position is inside the border and lies on a masked pixel is
+// lost with kMasked (TrkMaskArgs: one byte read per feature-frame).  The test
+// needs the frame's final position, so the residue is taken in place
+// (a.merge_res is ignored).  Kernels of their own in a code object of their own
+// (track7_mask.hip), like the motion-prior ones.
+template <bool AOS, int NL>
+__global__ __launch_bounds__(kBlock) void k_track7_mask(TrkArgs a, TrkFramesArgs b, TrkMaskArgs mk,
+                                                        float *__restrict__ fx, float *__restrict__ fy,
+                                                        int *__restrict__ fv, int n) {
+  __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF];
+  constexpr bool BAND = false, FAST = false, FB = false, LAZY = false, HOOK = false, MULTI = false, PRED = false,
+                 MASK = true;
+  const TrkFbArgs fb{};
+  const TrkMultiArgs ms{};
+  const TrkPredArgs pr{};
+#include "track7_body.h"
+}
+
+// ... and their lazy-gradient twins, for the batched calls whose banks hold
+// level 0 as the img plane alone (klt_hip_set_lazy_grad): the hook instances'
+// body (exit count and wave times, so that the tail schedule applies), the
+// deferred residue included.  The mask comes last in the argument segment
+// (T7MaskKArgs) and is read from there at the test.
+template <int NL>
+__global__ __launch_bounds__(kBlock, NL == 2 ? 5 : 4) void k_track7_mask_lazy(TrkArgs a, TrkFramesArgs b,
+                                                                               float *__restrict__ fx,
+                                                                               float *__restrict__ fy,
+                                                                               int *__restrict__ fv, int n,
+                                                                               TrkMaskArgs mk) {
+  __shared__ __attribute__((aligned(16))) float red_all[kWaves][kRedF + kPat];
+  constexpr bool BAND = false, AOS = true, FAST = false, LAZY = true, FB = false, HOOK = true, MULTI = false,
+                 PRED = false, MASK = true;
+  const TrkFbArgs fb{};
+  const TrkMultiArgs ms{};
+  const TrkPredArgs pr{};
 #include "track7_body.h"
 }
 
@@ -981,6 +1039,28 @@ hipError_t launch_track7_pred(hipStream_t st, const TrkArgs &a, const TrkFramesA
     hipLaunchKernelGGL((k_track7_pred<false, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, pr, x, y, v, n);
   return hipGetLastError();
 }
+#elif KLT_T7_MASK_UNIT
+// a: launch_track7's, with the bounds thresholds set
+hipError_t launch_track7_mask(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkMaskArgs &mk, float *x,
+                              float *y, int *v, int n, int grid, bool two, const char **name) {
+  if (a.lazy) {  // launch_track7 has checked the layout: interleaved levels, level 0 the img plane
+    if (name) *name = two ? "kltdev::k_track7_mask_lazy<2>" : "kltdev::k_track7_mask_lazy<0>";
+    if (two) hipLaunchKernelGGL((k_track7_mask_lazy<2>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y, v, n, mk);
+    else hipLaunchKernelGGL((k_track7_mask_lazy<0>), dim3(grid), dim3(kBlock), 0, st, a, b, x, y, v, n, mk);
+    return hipGetLastError();
+  }
+  if (name)
+    *name = a.aos && two ? "kltdev::k_track7_mask<true, 2>"
+            : a.aos      ? "kltdev::k_track7_mask<true, 0>"
+                         : "kltdev::k_track7_mask<false, 0>";
+  if (a.aos && two)
+    hipLaunchKernelGGL((k_track7_mask<true, 2>), dim3(grid), dim3(kBlock), 0, st, a, b, mk, x, y, v, n);
+  else if (a.aos)
+    hipLaunchKernelGGL((k_track7_mask<true, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, mk, x, y, v, n);
+  else
+    hipLaunchKernelGGL((k_track7_mask<false, 0>), dim3(grid), dim3(kBlock), 0, st, a, b, mk, x, y, v, n);
+  return hipGetLastError();
+}
 #else
 hipError_t launch_track7_multi(hipStream_t st, const TrkArgs &a_in, const TrkFramesArgs &b, const TrkMultiArgs &m,
                                float *x, float *y, int *v, int n, const char **name) {
@@ -1003,7 +1083,8 @@ hipError_t launch_track7_multi(hipStream_t st, const TrkArgs &a_in, const TrkFra
 }
 
 hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const TrkFramesArgs &b, float *x, float *y,
-                         int *v, int n, const char **name, const TrkFbArgs *fb, const TrkPredArgs *pr) {
+                         int *v, int n, const char **name, const TrkFbArgs *fb, const TrkPredArgs *pr,
+                         const TrkMaskArgs *mk) {
   TrkArgs a = a_in;
   for (int l = 0; l < KLT_HIP_MAX_LEVELS; ++l) {
     a.oobx[l] = oob_threshold(a.B[l].w);
@@ -1015,7 +1096,7 @@ hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const T
   // (interleaved levels are the fused path's, always two levels deep)
   const bool two = KLT_T7_NL2 && a.nlev == 2;
   if (fb) {  // the runtime refuses band calls and fast sums with the check on
-    if (band || a.fast || pr) return hipErrorInvalidValue;
+    if (band || a.fast || pr || mk) return hipErrorInvalidValue;
     if (name)
       *name = a.aos && two ? "kltdev::k_track7_fb<true, 2>"
               : a.aos      ? "kltdev::k_track7_fb<true, 0>"
@@ -1029,8 +1110,17 @@ hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a_in, const T
     return hipGetLastError();
   }
   if (pr) {  // the runtime refuses band calls, fast sums, lazy gradients and the checks with the prior on
-    if (band || a.fast || a.lazy || !pr->vx || !pr->vy) return hipErrorInvalidValue;
+    if (band || a.fast || a.lazy || mk || !pr->vx || !pr->vy) return hipErrorInvalidValue;
     return launch_track7_pred(st, a, b, *pr, x, y, v, n, grid, two, name);
+  }
+  if (mk) {  // the same refusals with the region mask's tracking use on
+    if (band || a.fast || !mk->mask || mk->pitch < a.ncols) return hipErrorInvalidValue;
+    if (a.lazy) {  // as below: whole-frame interleaved pyramids, level 0 of the bank an img plane
+      if (!a.aos || a.B[0].il != kLayoutImg) return hipErrorInvalidValue;
+      for (int l = 0; l < a.nlev; ++l)
+        if (a.A[l].w != a.B[l].w || a.A[l].h != a.B[l].h) return hipErrorInvalidValue;
+    }
+    return launch_track7_mask(st, a, b, *mk, x, y, v, n, grid, two, name);
   }
   if (a.lazy) {  // the runtime sends whole-frame interleaved pyramids here (fast sums: two levels)
     if (band || !a.aos || (a.fast && !two)) return hipErrorInvalidValue;

@@ -2,9 +2,9 @@
 // included inside each kernel: the FB-off kernels keep their by-value
 // arguments and compile to what they were before the forward-backward
 // instances existed.  The including kernel provides: the template parameters
-// BAND, AOS, NL, FAST, LAZY, HOOK; constexpr bool FB, MULTI, PRED; TrkArgs a;
-// TrkFramesArgs b; TrkFbArgs fb; TrkMultiArgs ms; TrkPredArgs pr; fx, fy, fv,
-// n; and the LDS array red_all.  The lazy-gradient instances run at their scalar register
+// BAND, AOS, NL, FAST, LAZY, HOOK; constexpr bool FB, MULTI, PRED, MASK; TrkArgs a;
+// TrkFramesArgs b; TrkFbArgs fb; TrkMultiArgs ms; TrkPredArgs pr; TrkMaskArgs mk;
+// fx, fy, fv, n; and the LDS array red_all.  The lazy-gradient instances run at their scalar register
 // limit; what LATE, ROLL and the pinned lane numbers below do for them keeps
 // spilled scalars and argument loads out of their frame loop (DESIGN section 4,
 // "Scalar spills off the lazy tracker's chain").  Every other instance
@@ -13,6 +13,8 @@
   // there (track7.hip's T7KArgs: the arguments of k_track7 / k_track7_hook)
   constexpr bool LATE = LAZY && !FB && !MULTI;
   static_assert(!PRED || (!FB && !MULTI && !LAZY && !BAND && !FAST && !HOOK), "k_track7_pred: full records, exact sums");
+  static_assert(!MASK || (!FB && !MULTI && !BAND && !FAST && !PRED && LAZY == HOOK),
+                "k_track7_mask: exact sums on full records, k_track7_mask_lazy: the lazy-gradient hook instances");
   static_assert(!HOOK || LATE, "wave_exit reads T7KArgs");
   if (a.prio) __builtin_amdgcn_s_setprio(3);  // the chain issues ahead of co-resident pyramid waves
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
@@ -59,7 +61,7 @@
   float x = u(fx[f]), y = u(fy[f]);
   int v = u(fv[f]);
   const int nlev = NL > 0 ? NL : a.nlev;
-  const bool merge = !FB && !PRED && a.merge_res && nlev >= 2;
+  const bool merge = !FB && !PRED && (!MASK || LAZY) && a.merge_res && nlev >= 2;
   // PRED (klt_hip_set_predict): the feature's last displacement, wave-uniform
   // over the frames; loaded with the list, stored with it by lane 0
   float pvx = 0.0f, pvy = 0.0f;
@@ -144,6 +146,32 @@
       if (!lost_prev) {
         const bool border = xo < a.borderx || xo > a.ncols - 1 - a.borderx || yo < a.bordery ||
                             yo > a.nrows - 1 - a.bordery;
+        // MASK (klt_hip_set_mask): a test of position like the border's, after it.
+        // Every level ran unless the loop broke (SMALL_DET is left alone, OOB
+        // comes first), so (xo, yo) is a level-0 position: on a masked pixel the
+        // frame's status is kMasked whatever the residue or the iteration count
+        // and a residue verdict deferred to the next frame is dropped: the
+        // tentative position is tested at once.  One byte per feature-frame, at a
+        // wave-uniform address.  The lazy-gradient instances read the mask's
+        // pointer and pitch from the argument segment here, frame by frame (two
+        // scalar loads the compiler may not hoist), so that they hold no scalar
+        // registers over the frame loop
+        if constexpr (MASK)
+          if (val != kOOB && !border && val != kSmallDet && xo >= 0.0f && yo >= 0.0f && xo < (float)a.ncols &&
+              yo < (float)a.nrows) {
+            const unsigned char *mp = mk.mask;
+            long mpitch = mk.pitch;
+            if constexpr (LATE) {
+              T7MaskKArgsPtr ka = t7_mask_kargs();
+              asm volatile("" : "+s"(ka));
+              mp = ka->mk.mask;
+              mpitch = ka->mk.pitch;
+            }
+            if (mp[(long)u((int)yo) * mpitch + u((int)xo)] == 0) {
+              val = kMasked;
+              pd.on = false;
+            }
+          }
         if (val == kOOB || border) {
           pd.on = false;  // outside the border: OOB whatever the residue (trackFeatures.c:1383-1398)
           x = -1.0f;

@@ -115,6 +115,9 @@ DEVICE_PROTOS = {
     "klt_hip_set_predict": (C.c_int, [V, C.c_int, V, V]),
     "klt_hip_get_predict": (C.c_int, [V, IP, C.POINTER(V), C.POINTER(V)]),
     "klt_hip_set_predict_table": (C.c_int, [V, V, V, C.c_long]),
+    # dev_mask, pitch, flags (MASK_SELECT | MASK_TRACK)
+    "klt_hip_set_mask": (C.c_int, [V, V, C.c_long, C.c_int]),
+    "klt_hip_get_mask": (C.c_int, [V, C.POINTER(V), C.POINTER(C.c_long), IP]),
     "klt_hip_set_frames_affine": (C.c_int, [V, C.POINTER(AffineDesc), V, V]),
     "klt_hip_get_frames_affine": (C.c_int, [V, IP]),
     "klt_hip_set_affine_table": (C.c_int, [V, V, V, C.c_long]),
@@ -227,6 +230,8 @@ DEVICE_PROTOS = {
     "klt_amd_set_reduction": (None, [V, C.c_int]),
     "klt_amd_set_fb_check": (C.c_int, [V, C.c_int, C.c_float]),
     "klt_amd_set_prediction": (C.c_int, [V, C.c_int]),
+    # host_mask (ncols x nrows bytes), ncols, nrows, flags
+    "klt_amd_set_mask": (C.c_int, [V, V, C.c_int, C.c_int, C.c_int]),
     "klt_amd_release_cached_devices": (C.c_int, []),
     "klt_amd_register_buffer": (C.c_int, [V, V, C.c_size_t]),
     "klt_amd_unregister_buffer": (C.c_int, [V, V]),
@@ -238,6 +243,8 @@ DEVICE_PROTOS = {
 }
 
 H2D, D2H, D2D = 1, 2, 3  # hipMemcpyKind
+MASK_SELECT, MASK_TRACK = 1, 2  # klt_hip_set_mask's flags
+MASKED = -7  # KLT_HIP_MASKED / KLT_AMD_MASKED
 
 
 def bind_device(lib: C.CDLL) -> C.CDLL:

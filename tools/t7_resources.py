@@ -6,7 +6,8 @@
 A .hip file is compiled with the HIPFLAGS of csrc/Makefile (read from it) plus
 --cuda-device-only -S; `make resources` runs this for every kernel file
 (track7_pred.hip is the code object of the k_track7_pred instances:
-tools/t7_resources.py csrc/track7_pred.hip --loop k_track7_pred).
+tools/t7_resources.py csrc/track7_pred.hip --loop k_track7_pred; track7_mask.hip
+that of k_track7_mask and k_track7_mask_lazy).
 Per kernel, from the code object's metadata: VGPRs, SGPRs, scalar and vector
 spill counts, scratch and LDS.  Then static instruction counts of the kernel's
 whole text ("all") and of its largest outermost loop ("loop": the trackers'
