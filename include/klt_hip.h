@@ -38,7 +38,19 @@ extern "C" {
 
 /* reduction order inside the Newton loop */
 #define KLT_HIP_EXACT 0 /* reference order: bit-identical to the CPU path */
-#define KLT_HIP_FAST 1  /* wave64 shuffle tree: not bit-identical (tolerance) */
+/* KLT_HIP_FAST: each window sum -- gxx, gxy, gyy, ex, ey, the residue and, in
+   lighting-insensitive mode, the gain/bias moments -- is a float32 sum of the
+   reference's terms in an unspecified order (a wave64 tree); everything else
+   is as in KLT_HIP_EXACT.  Not bit-identical, and the order may differ between
+   kernels, schedules and releases.  What the tests hold it to
+   (tests/sum_scenes.py, tests/test_gpu_fast_sums.py): tracked one frame from
+   the same start, at most 0.5 % of the features differ in status from, or lie
+   more than B ulps of a coordinate from, the same tracker with float64 sums;
+   B is 4 or 8 ulps by configuration, four times the 99th percentile of
+   float32 sums in seven orders on the CPU
+   (tests/golden/fast_sums_160x120.json).  Over a sequence the differences
+   compound (tests/test_gpu_long.py: 0.5 px, 1e-3 of the statuses). */
+#define KLT_HIP_FAST 1
 
 /* taps exactly as _computeKernels produces them: k[0..width-1], un-reversed */
 typedef struct {

@@ -97,6 +97,10 @@ TrkLevel prev_level(klt_hip_ctx *c, int l) {
 
 bool bank_fits(const Bank &K, const klt_hip_pyr_desc *d, int F) {
   if (K.nlev != d->nlevels) return false;
+  // the level sizes below follow the bank's own subsampling: a bank laid out
+  // for another one (a context reused for a pyramid of the same depth) does
+  // not fit, whatever its first level's size
+  if (K.ss != (d->nlevels > 1 ? d->subsampling : 1)) return false;
   int w = d->ncols, h = d->nrows;
   for (int l = 0; l < d->nlevels; ++l) {
     const Level &L = K.lv[l];
@@ -496,6 +500,15 @@ int build_chunk(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, int bi
       if (build_pyramid_on(c, kScratchSlot, q.pd, src + (long)f * q.stride, q.pitch, 0, ps)) return -1;
       for (int l = 0; l < q.pd->nlevels; ++l)  // generic levels: planes
         if (copy_level(c, level_view(c->slot[kScratchSlot].lv[l]), K.lv[l], f, ps)) return -1;
+    }
+    // whole frames: every row is valid.  The bank's last frame is the next
+    // chunk's previous pyramid (prev_level reads K.vlo / K.vhi); left at zero,
+    // or at an earlier fused build's band, the generic tracker's band test took
+    // every window of that pyramid for missing rows and wrote its escape flag,
+    // a null pointer in a call without bands
+    for (int l = 0; l < q.pd->nlevels; ++l) {
+      K.vlo[l] = 0;
+      K.vhi[l] = 1 << 30;
     }
   }
   return 0;
