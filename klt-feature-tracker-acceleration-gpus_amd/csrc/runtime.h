@@ -74,6 +74,62 @@ struct Bank {
   float *hs = nullptr;  // per-frame row pass of the sigma-3.6 smoothing (fused path)
   size_t hs_cap = 0;
   int vlo[KLT_HIP_MAX_LEVELS] = {}, vhi[KLT_HIP_MAX_LEVELS] = {};  // rows built (band mode: a subset)
+
+  // What the bank holds after a build, called by every build and by nothing
+  // else: level 0 in layout il, the levels above interleaved under an
+  // image-only level 0 and in il otherwise, and the valid rows of every level
+  // (null: whole frames).  The only writer of a bank level's il and of vlo / vhi.
+  void holds(int il, const int *lo = nullptr, const int *hi = nullptr) {
+    for (int l = 0; l < nlev; ++l) {
+      lv[l].il = l > 0 && il == kLayoutImg ? kLayoutRec : il;
+      vlo[l] = lo ? lo[l] : 0;
+      vhi[l] = hi ? hi[l] : 1 << 30;
+    }
+  }
+  // frame f of level l with its valid rows
+  TrkLevel level(int l, long f) const { return level_view(lv[l], f, vlo[l], vhi[l]); }
+};
+
+// a bank whose pyramids a band call built ahead, during its own tracking, for
+// the next call (klt_hip_track_frames_band's next_frames); bank -1: none
+struct BuiltAhead {
+  int bank = -1, F = 0, row_lo = 0, row_hi = 0, il = 1;
+  const unsigned char *src = nullptr;
+  long stride = 0;
+  bool same(const BuiltAhead &o) const {
+    return F == o.F && row_lo == o.row_lo && row_hi == o.row_hi && il == o.il && src == o.src && stride == o.stride;
+  }
+};
+
+// The three banks of the batched calls, taken in turn ("Banks").
+// ensure_banks / free_banks (runtime_pyr.hip) lay them out; take, peek,
+// built_ahead and drop_ahead are the only code that touches next and pre;
+// Bank::holds records every build.
+struct BankRing {
+  Bank bank[3];  // views into arena
+  void *arena = nullptr;
+  size_t arena_bytes = 0;
+  int next = 0;
+  BuiltAhead pre;
+  hipEvent_t ev_built[3] = {}, ev_free[3] = {};
+
+  // the next bank in turn.  A build-ahead record for it goes: the bank is
+  // taken as built (*prebuilt, when it holds what `want` describes) or is
+  // about to be overwritten
+  int take(const BuiltAhead *want = nullptr, bool *prebuilt = nullptr) {
+    const int bi = next;
+    next = (bi + 1) % 3;
+    if (prebuilt) *prebuilt = want && pre.bank == bi && pre.same(*want);
+    if (pre.bank == bi) pre.bank = -1;
+    return bi;
+  }
+  int peek() const { return next; }  // the bank the next take() returns: a build-ahead's
+  void built_ahead(const BuiltAhead &b) { pre = b; }
+  bool drop_ahead() {  // the record goes (the banks are laid out again, or change hands); true: there was one
+    const bool was = pre.bank >= 0;
+    pre.bank = -1;
+    return was;
+  }
 };
 
 // where the pyramid preceding the next batch lives
@@ -253,23 +309,12 @@ struct __attribute__((visibility("default"))) klt_hip_ctx {  // its constructor 
   HostPool *pool = nullptr;
   int copy_threads = default_host_threads();  // pool workers besides the caller (0: the caller alone)
   unsigned long long *prof = nullptr;  // instrumented build: per-wave tracker phase counters
-  Bank bank[3];  // views into bank_arena
-  void *bank_arena = nullptr;
-  size_t bank_arena_bytes = 0;
+  BankRing banks;
   size_t bank_budget = 0;  // bytes the bank arena may take (klt_hip_set_bank_budget; 0: the default)
   size_t dev_total = 0;    // the device's memory (queried once, for the default budget)
   int chunk_used = 0;      // frames per bank of the last klt_hip_track_frames* call (budget-capped)
-  int bank_next = 0;
-  // band mode: a bank whose pyramids were built ahead, during the previous
-  // call's tracking (klt_hip_track_frames_band's next_frames); -1: none
-  struct {
-    int bank = -1, F = 0, row_lo = 0, row_hi = 0, il = 1;
-    const unsigned char *src = nullptr;
-    long stride = 0;
-  } pre;
-  PrevRef prev;
+  PrevRef prev;            // the kept pyramid (prev_level, kept_* below), current while frames_ready
   bool frames_ready = false;
-  hipEvent_t ev_bbuilt[3] = {}, ev_bfree[3] = {};
   bool timing = false;
   long frames_timed[T_N] = {};
   std::vector<hipEvent_t> ev_pool;
@@ -471,8 +516,36 @@ inline int mask_refused(klt_hip_ctx *c, int ncols, const char *who) {
   return fail(c, "%s: region mask pitch %ld < image width %d (klt_hip_set_mask)", who, c->mask_pitch, ncols);
 }
 
+// The kept pyramid: the one the next batched call starts from, in a slot or a
+// frame of a bank (c->prev).  Level l, its depth and subsampling, and whether
+// its level 0 is the img plane alone (klt_hip_set_lazy_grad).
+inline TrkLevel prev_level(const klt_hip_ctx *c, int l) {
+  return c->prev.bank < 0 ? level_view(c->slot[c->prev.slot].lv[l]) : c->banks.bank[c->prev.bank].level(l, c->prev.frame);
+}
+inline int kept_nlev(const klt_hip_ctx *c) {
+  return c->prev.bank < 0 ? c->slot[c->prev.slot].nlev : c->banks.bank[c->prev.bank].nlev;
+}
+inline int kept_ss(const klt_hip_ctx *c) {
+  return c->prev.bank < 0 ? c->slot[c->prev.slot].ss : c->banks.bank[c->prev.bank].ss;
+}
+inline bool kept_image_only(const klt_hip_ctx *c) { return prev_level(c, 0).il == kLayoutImg; }  // slots hold whole levels
+
+// the selection grid over a w x h image: every step-th pixel inside the
+// borders, and the window's half sizes
+struct SelGrid {
+  int nx, ny, step, hw, hh;
+};
+inline int sel_step(const klt_hip_select_desc &d) { return d.nSkippedPixels + 1; }
+inline SelGrid sel_grid(const klt_hip_select_desc &d, int w, int h) {
+  const int step = sel_step(d), cx = w - 2 * d.borderx, cy = h - 2 * d.bordery;
+  const bool ok = step > 0;  // the callers refuse step < 1
+  return SelGrid{ok && cx > 0 ? (cx + step - 1) / step : 0, ok && cy > 0 ? (cy + step - 1) / step : 0, step,
+                 d.window_width / 2, d.window_height / 2};
+}
+
 // runtime.hip
 int ensure_pipeline(klt_hip_ctx *c);
+int forget_kept(klt_hip_ctx *c);  // no current pyramid and no build-ahead from here on
 // runtime_pyr.hip
 bool fused_ok(const klt_hip_pyr_desc *d);
 int ensure_slot(klt_hip_ctx *c, int s, const klt_hip_pyr_desc *d);
@@ -482,12 +555,14 @@ size_t bank_arena_bytes(const klt_hip_pyr_desc *d, int frames);
 void free_banks(klt_hip_ctx *c);
 size_t bank_budget_of(klt_hip_ctx *c);
 int budget_chunk(klt_hip_ctx *c, const klt_hip_pyr_desc *d);
+bool banks_fit(const klt_hip_ctx *c, const klt_hip_pyr_desc *d, int frames);
 int ensure_banks(klt_hip_ctx *c, const klt_hip_pyr_desc *d, int frames);
 int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const uint8_t *src, long pitch,
                      long stride, int F, hipStream_t st, int row_lo = 0, int row_hi = 1 << 30, int plane_lo = 0,
                      int plane_hi = 1 << 30, int il = 1, long first = 0, long step = 1);
 // runtime_frames.hip
-bool bank_fits(const Bank &K, const klt_hip_pyr_desc *d, int F);
+int tables_refused(klt_hip_ctx *c, const char *who, const float *tab_x, const float *tab_y, const int *tab_val,
+                   long tab_stride, int n, long pitch, int ncols);  // the table arrays and the frames' pitch
 int replace_desc_refused(klt_hip_ctx *c, const klt_hip_replace_desc *d, const char *who);  // klt_hip_set_frames_replace's checks
 // runtime_track.hip
 int check_window(klt_hip_ctx *c, const klt_hip_track_desc *d);

@@ -187,8 +187,8 @@ KLT_API void klt_hip_ctx_destroy(klt_hip_ctx *c) {
   }
   free_banks(c);
   for (int k = 0; k < 3; ++k) {
-    if (c->ev_bbuilt[k]) hipEventDestroy(c->ev_bbuilt[k]);
-    if (c->ev_bfree[k]) hipEventDestroy(c->ev_bfree[k]);
+    if (c->banks.ev_built[k]) hipEventDestroy(c->banks.ev_built[k]);
+    if (c->banks.ev_free[k]) hipEventDestroy(c->banks.ev_free[k]);
   }
   hipFree(c->d_perm);
   hipFree(c->d_count);
@@ -242,6 +242,13 @@ KLT_API void klt_hip_ctx_destroy(klt_hip_ctx *c) {
   delete c;
 }
 
+int forget_kept(klt_hip_ctx *c) {
+  if (c->banks.drop_ahead() && c->pstream) HIPCHK(c, hipStreamSynchronize(c->pstream));  // a band call's build-ahead
+  c->frames_ready = false;
+  c->prev = PrevRef{};
+  return 0;
+}
+
 KLT_API int klt_hip_current_device(void) {
   int d = 0;
   if (hipGetDevice(&d) != hipSuccess) return -1;
@@ -256,12 +263,12 @@ constexpr size_t kKeepBytes = (size_t)2 << 30;
 
 KLT_API size_t klt_hip_ctx_footprint(klt_hip_ctx *c) {
   if (!c) return 0;
-  size_t b = c->bank_arena_bytes + c->ring_cap + c->drows_cap + c->hs_cap * sizeof(float) +
+  size_t b = c->banks.arena_bytes + c->ring_cap + c->drows_cap + c->hs_cap * sizeof(float) +
              c->eig_cap * sizeof(int) + c->u8_cap * 2 + (c->tmp_cap[0] + c->tmp_cap[1]) * sizeof(float);
   for (const auto &S : c->slot)
     for (const auto &L : S.lv) b += 3 * L.cap * sizeof(float);
-  if (!c->bank_arena)
-    for (const auto &K : c->bank) {
+  if (!c->banks.arena)
+    for (const auto &K : c->banks.bank) {
       for (const auto &L : K.lv) b += 3 * L.cap * sizeof(float);
       b += K.hs_cap * sizeof(float);
     }
@@ -289,7 +296,6 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
     c->h_stage = nullptr;
     c->h_rows = nullptr;
     c->stage_cap = c->hrows_cap = 0;
-    c->prev = PrevRef{};
   }
   if (c->copy_threads != default_host_threads()) {
     delete c->pool;  // idle between calls; joined here
@@ -340,8 +346,7 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->wave_t = nullptr;
   c->ahead_ready = 0;
   c->prof = nullptr;
-  c->frames_ready = false;
-  c->pre.bank = -1;
+  if (forget_kept(c)) return -1;
   c->timing = false;
   for (int k = 0; k < T_N; ++k) {
     for (auto &p : c->ev_used[k]) {
@@ -752,14 +757,11 @@ KLT_API int klt_hip_min_eigen(klt_hip_ctx *c, int s, const klt_hip_select_desc *
   if (!c || !d) return fail(c, "min_eigen: null argument");
   if (s < 0 || s >= KLT_HIP_MAX_SLOTS || c->slot[s].nlev < 1) return fail(c, "min_eigen: bad slot");
   const Level &L = c->slot[s].lv[0];
-  const int hw = d->window_width / 2, hh = d->window_height / 2;
-  const int step = d->nSkippedPixels + 1;
+  const SelGrid g = sel_grid(*d, L.w, L.h);
+  const int hw = g.hw, hh = g.hh, step = g.step, gx = g.nx, gy = g.ny;
   if (step < 1) return fail(c, "min_eigen: bad nSkippedPixels");
   const int bx = d->borderx, by = d->bordery;
   if (bx < hw || by < hh) return fail(c, "min_eigen: border smaller than window half size");
-  const int cx = L.w - 2 * bx, cy = L.h - 2 * by;
-  const int gx = cx > 0 ? (cx + step - 1) / step : 0;
-  const int gy = cy > 0 ? (cy + step - 1) / step : 0;
   *nx = gx;
   *ny = gy;
   if (!vals) return 0;
@@ -785,12 +787,12 @@ static int eigen_to_dev(klt_hip_ctx *c, int s, const klt_hip_select_desc *d, int
   const long np = (long)*nx * *ny;
   if (np == 0) return 0;
   const Level &L = c->slot[s].lv[0];
+  const SelGrid g = sel_grid(*d, L.w, L.h);
   if (grow(c, &c->d_eig, &c->eig_cap, (size_t)np)) return -1;
   TimedScope ts(c, T_EIG, c->stream);
   return launched(c, "k_min_eigen", launch_min_eigen(c->stream, L.il ? L.img + kRecGx : L.gx, L.il ? L.img + kRecGy : L.gy,
-                                                     L.w, L.il ? 3 : 1, d->borderx, d->bordery,
-                                                     d->nSkippedPixels + 1, *nx, *ny, d->window_width / 2,
-                                                     d->window_height / 2, c->d_eig, &c->eig_kernel));
+                                                     L.w, L.il ? 3 : 1, d->borderx, d->bordery, g.step, g.nx, g.ny, g.hw,
+                                                     g.hh, c->d_eig, &c->eig_kernel));
 }
 
 static SelEngine *sel_of(klt_hip_ctx *c) {
@@ -811,8 +813,7 @@ KLT_API int klt_hip_select(klt_hip_ctx *c, int s, const klt_hip_select_desc *d, 
   int nx = 0, ny = 0;
   if (eigen_to_dev(c, s, d, &nx, &ny)) return -1;
   std::string e;
-  if (sel_engine_run(sel_of(c), c->stream, c->d_eig, nx, ny, d->borderx, d->bordery, d->nSkippedPixels + 1, ncols,
-                     nrows, mindist < 0 ? 0 : mindist, min_eigenvalue, overwrite_all, x, y, val, changed, n, sel_mask(c),
+  if (sel_engine_run(sel_of(c), c->stream, c->d_eig, nx, ny, d->borderx, d->bordery, sel_step(*d), ncols, nrows, mindist < 0 ? 0 : mindist, min_eigenvalue, overwrite_all, x, y, val, changed, n, sel_mask(c),
                      c->mask_pitch, &e))
     return fail(c, "select: %s", e.c_str());
   return 0;
@@ -827,8 +828,7 @@ KLT_API int klt_hip_select_dev_map(klt_hip_ctx *c, const int *dev_map, int nx, i
   if (mask_refused(c, ncols, "select_dev_map")) return -1;
   if (use_device(c)) return -1;
   std::string e;
-  if (sel_engine_run(sel_of(c), c->stream, dev_map, nx, ny, d->borderx, d->bordery, d->nSkippedPixels + 1, ncols,
-                     nrows, mindist < 0 ? 0 : mindist, min_eigenvalue, overwrite_all, x, y, val, changed, n, sel_mask(c),
+  if (sel_engine_run(sel_of(c), c->stream, dev_map, nx, ny, d->borderx, d->bordery, sel_step(*d), ncols, nrows, mindist < 0 ? 0 : mindist, min_eigenvalue, overwrite_all, x, y, val, changed, n, sel_mask(c),
                      c->mask_pitch, &e))
     return fail(c, "select: %s", e.c_str());
   return 0;

@@ -1,7 +1,7 @@
 // runtime_frames.hip -- host side of libklt_amd.so: the batched calls
 // (klt_hip_track_frames, _host, _band), their schedule, and the pyramid kept
 // from one call to the next (runtime.h).  No kernels here.
-#include "runtime.h"
+#include "replace_step.h"
 
 // A/B in one tree: KLT_FRAMES_SCHED=0..3 replaces whatever
 // klt_hip_set_frames_overlap was given, KLT_FRAMES_TAIL=K whatever
@@ -81,44 +81,17 @@ struct SeqStages {
 // batched frames: pyramids of `chunk` frames per pair of launches into one of
 // three banks on the pyramid stream, one k_track_frames launch per chunk on
 // the tracking stream.  Bank k is rebuilt only after the chunk that used its
-// last frame as the previous pyramid has been tracked (ev_bfree[k]).
+// last frame as the previous pyramid has been tracked (banks.ev_free[k]).
 // ---------------------------------------------------------------------------
 
 namespace {
 constexpr int kSeedSlot = KLT_HIP_MAX_SLOTS, kScratchSlot = KLT_HIP_MAX_SLOTS + 1;
 
-TrkLevel prev_level(klt_hip_ctx *c, int l) {
-  if (c->prev.bank < 0) return level_view(c->slot[c->prev.slot].lv[l]);
-  const Bank &K = c->bank[c->prev.bank];
-  return level_view(K.lv[l], c->prev.frame, K.vlo[l], K.vhi[l]);
-}
-
-}  // namespace
-
-bool bank_fits(const Bank &K, const klt_hip_pyr_desc *d, int F) {
-  if (K.nlev != d->nlevels) return false;
-  // the level sizes below follow the bank's own subsampling: a bank laid out
-  // for another one (a context reused for a pyramid of the same depth) does
-  // not fit, whatever its first level's size
-  if (K.ss != (d->nlevels > 1 ? d->subsampling : 1)) return false;
-  int w = d->ncols, h = d->nrows;
-  for (int l = 0; l < d->nlevels; ++l) {
-    const Level &L = K.lv[l];
-    if (L.w != w || L.h != h || !L.img || L.cap < (size_t)(w > 0 ? w : 1) * (h > 0 ? h : 1) * F) return false;
-    w /= K.ss;
-    h /= K.ss;
-  }
-  if (d->nlevels == 2 && K.hs_cap < (size_t)(K.lv[1].w > 0 ? K.lv[1].w : 1) * d->nrows * F) return false;
-  return true;
-}
-
-namespace {
-
 // one level (a view: a slot's, or a bank frame's) into frame f of level `to`
-// (a slot's: f = 0), in its layout
+// (a slot's: f = 0), in the view's layout; what `to` holds is its owner's to
+// record (slot_level below, Bank::holds)
 int copy_level(klt_hip_ctx *c, const TrkLevel &from, Level &to, long f, hipStream_t st) {
   const size_t n = (size_t)from.w * from.h, b = sizeof(float) * n;
-  to.il = from.il;
   if (!b) return 0;
   if (from.il) {
     HIPCHK(c, hipMemcpyAsync(to.img + 3 * f * n, from.img, 3 * b, hipMemcpyDeviceToDevice, st));
@@ -130,16 +103,22 @@ int copy_level(klt_hip_ctx *c, const TrkLevel &from, Level &to, long f, hipStrea
   return 0;
 }
 
+// a level of the kept pyramid into a slot's, which holds it in that layout
+int slot_level(klt_hip_ctx *c, const TrkLevel &from, Level &to, hipStream_t st) {
+  to.il = from.il;
+  return copy_level(c, from, to, 0, st);
+}
+
 // a klt_hip_pyr_desc shaped like the kept pyramid (the sizes ensure_slot
 // reads); *ss: its subsampling as kept (1 for a single level)
 klt_hip_pyr_desc prev_desc(klt_hip_ctx *c, int *ss) {
   const TrkLevel p0 = prev_level(c, 0);
-  *ss = c->prev.bank < 0 ? c->slot[c->prev.slot].ss : c->bank[c->prev.bank].ss;
+  *ss = kept_ss(c);
   klt_hip_pyr_desc d;
   memset(&d, 0, sizeof d);
   d.ncols = p0.w;
   d.nrows = p0.h;
-  d.nlevels = c->prev.bank < 0 ? c->slot[c->prev.slot].nlev : c->bank[c->prev.bank].nlev;
+  d.nlevels = kept_nlev(c);
   d.subsampling = *ss > 1 ? *ss : 2;
   return d;
 }
@@ -150,7 +129,7 @@ klt_hip_pyr_desc prev_desc(klt_hip_ctx *c, int *ss) {
 int prev_to_seed(klt_hip_ctx *c, int from, hipStream_t st) {
   Slot &S = c->slot[kSeedSlot];
   for (int l = from; l < S.nlev; ++l)
-    if (copy_level(c, prev_level(c, l), S.lv[l], 0, st)) return -1;
+    if (slot_level(c, prev_level(c, l), S.lv[l], st)) return -1;
   c->prev = PrevRef{-1, 0, kSeedSlot};
   return 0;
 }
@@ -165,9 +144,7 @@ int prev_to_seed(klt_hip_ctx *c, int from, hipStream_t st) {
 // the levels above copied.  On the tracking stream, which has already waited
 // for the bank's build.
 int prev_full(klt_hip_ctx *c) {
-  if (c->prev.bank < 0) return 0;  // slots always hold whole levels
-  const Bank &K = c->bank[c->prev.bank];
-  if (K.lv[0].il != kLayoutImg) return 0;
+  if (!kept_image_only(c)) return 0;
   const TrkLevel p0 = prev_level(c, 0);
   int ss = 1;
   const klt_hip_pyr_desc d = prev_desc(c, &ss);
@@ -231,8 +208,18 @@ KLT_API int klt_hip_frames_end_slot(klt_hip_ctx *c, int slot) {
   for (int l = 0; l < nl; ++l) {
     const TrkLevel p = prev_level(c, l);
     if (p.w != S.lv[l].w || p.h != S.lv[l].h) return fail(c, "frames_end_slot: level %d size mismatch", l);
-    if (copy_level(c, p, S.lv[l], 0, c->stream)) return -1;
+    if (slot_level(c, p, S.lv[l], c->stream)) return -1;
   }
+  return 0;
+}
+
+int tables_refused(klt_hip_ctx *c, const char *who, const float *tab_x, const float *tab_y, const int *tab_val,
+                   long tab_stride, int n, long pitch, int ncols) {
+  const int ntab = (tab_x != nullptr) + (tab_y != nullptr) + (tab_val != nullptr);
+  if (ntab != 0 && ntab != 3) return fail(c, "%s: give all three table arrays or none", who);
+  if (ntab && tab_stride < n) return fail(c, "%s: table stride %ld < n %d", who, tab_stride, n);
+  if (pitch < (long)ncols * frame_bpp(c->frame_format))
+    return fail(c, "%s: pitch %ld < ncols %d * %d bytes per pixel", who, pitch, ncols, frame_bpp(c->frame_format));
   return 0;
 }
 
@@ -286,15 +273,10 @@ int frames_check(klt_hip_ctx *c, const FramesCall &q, int chunk) {
   if (q.nframes < 0 || chunk < 1 || n < 0) return fail(c, "track_frames: bad nframes/chunk/n");
   if (q.nframes > 0 && !q.frames) return fail(c, "track_frames: null frames");
   if (n > 0 && (!q.x || !q.y || !q.val)) return fail(c, "track_frames: null feature arrays");
-  const int ntab = (q.tab_x != nullptr) + (q.tab_y != nullptr) + (q.tab_val != nullptr);
-  if (ntab != 0 && ntab != 3) return fail(c, "track_frames: give all three table arrays or none");
-  if (ntab && q.tab_stride < n) return fail(c, "track_frames: table stride %ld < n %d", q.tab_stride, n);
-  if (q.band && c->frame_format != KLT_HIP_FRAME_GRAY8)
+  if (q.band && c->frame_format != KLT_HIP_FRAME_GRAY8)  // (a band call has no tables)
     return fail(c, "track_frames_band: colour frames are not covered (klt_hip_set_frame_format %d); convert with "
                 "klt_hip_to_gray", c->frame_format);
-  if (q.pitch < (long)pd->ncols * frame_bpp(c->frame_format))
-    return fail(c, "track_frames: pitch %ld < ncols %d * %d bytes per pixel", q.pitch, pd->ncols,
-                frame_bpp(c->frame_format));
+  if (tables_refused(c, "track_frames", q.tab_x, q.tab_y, q.tab_val, q.tab_stride, n, q.pitch, pd->ncols)) return -1;
   if (check_window(c, q.td)) return -1;
   if (c->rep_on && c->aff_on)
     return fail(c, "track_frames: the affine check does not combine with the replacement of lost features "
@@ -302,7 +284,7 @@ int frames_check(klt_hip_ctx *c, const FramesCall &q, int chunk) {
   if (track_refused(c, q.td, q.band != nullptr, n, q.band ? "track_frames_band" : "track_frames")) return -1;
   if (mask_refused(c, pd->ncols, q.band ? "track_frames_band" : "track_frames")) return -1;
   const TrkLevel p0 = prev_level(c, 0);
-  const int nl = c->prev.bank < 0 ? c->slot[c->prev.slot].nlev : c->bank[c->prev.bank].nlev;
+  const int nl = kept_nlev(c);
   if (p0.w != pd->ncols || p0.h != pd->nrows || nl != pd->nlevels)
     return fail(c, "track_frames: frames are %dx%d/%d levels, previous pyramid %dx%d/%d", pd->ncols, pd->nrows,
                 pd->nlevels, p0.w, p0.h, nl);
@@ -416,20 +398,14 @@ int frames_resources(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p) {
   c->chunk_used = p.chunk;
   // banks hold `chunk` frames whatever this call's length, so a short first
   // call does not force a reallocation (and a drain) in the next one
-  if (!(bank_fits(c->bank[0], pd, p.chunk) && bank_fits(c->bank[1], pd, p.chunk) &&
-        bank_fits(c->bank[2], pd, p.chunk))) {
-    // (re)allocation: drain both streams; a previous pyramid living in a bank
-    // moves to the seed slot first
-    if (prev_full(c)) return -1;  // an image-only frame: whole, in the seed slot (drained below)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->pstream));
-    if (c->prev.bank >= 0) {
-      if (ensure_slot(c, kSeedSlot, pd) || prev_to_seed(c, 0, c->stream)) return -1;
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if (ensure_banks(c, pd, p.chunk)) return -1;
-    c->pre.bank = -1;
+  if (!banks_fit(c, pd, p.chunk)) {
+    // they are laid out again: a previous pyramid living in a bank moves to
+    // the seed slot first (an image-only frame: whole), on the tracking stream,
+    // which has waited for that bank's build and is drained with the rest
+    if (prev_full(c)) return -1;
+    if (c->prev.bank >= 0 && (ensure_slot(c, kSeedSlot, pd) || prev_to_seed(c, 0, c->stream))) return -1;
   }
+  if (ensure_banks(c, pd, p.chunk)) return -1;
   if (p.tail) {
     const bool fresh = !c->d_exits || !c->d_exit_sig;
     if (!c->d_exits) HIPCHK(c, hipMalloc((void **)&c->d_exits, sizeof(unsigned long long)));
@@ -457,7 +433,7 @@ int frames_resources(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p) {
 // (profiles/r05_rank_timeline_*.txt)
 // Every event record and cross-stream wait is a packet the tracking queue
 // processes between two trackers (several us each), so the ahead-ready
-// band call records ev_start only when a build needs it, and no ev_bfree
+// band call records ev_start only when a build needs it, and no banks.ev_free
 // (its build-ahead waits for ev_go, which follows the previous tracker)
 struct PstreamBehind {
   bool serial, ahead;
@@ -478,17 +454,17 @@ struct PstreamBehind {
 int build_chunk(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, int bi, int F, const unsigned char *src,
                 hipStream_t ps, bool prebuilt, PstreamBehind &behind, TailRelease &rel) {
   const BandSpec *band = q.band;
-  Bank &K = c->bank[bi];
+  Bank &K = c->banks.bank[bi];
   // one stream: stream order is the dependency (an event wait would add a queue barrier)
   if (!p.serial && !prebuilt && behind(c)) return -1;  // this chunk's own frames: behind the caller's work
-  if (!p.serial && !prebuilt && !p.ahead) HIPCHK(c, hipStreamWaitEvent(ps, c->ev_bfree[bi], 0));
-  // tail: a hint on top of ev_bfree / ev_bbuilt, which stay the dependencies.
+  if (!p.serial && !prebuilt && !p.ahead) HIPCHK(c, hipStreamWaitEvent(ps, c->banks.ev_free[bi], 0));
+  // tail: a hint on top of banks.ev_free / banks.ev_built, which stay the dependencies.
   // The tracker that raises the count to rel.thr was enqueued for the
   // previous chunk and reaches it by completing.
   if (rel.wait) HIPCHK(c, hipStreamWaitValue32(ps, c->d_exit_sig, rel.thr, hipStreamWaitValueGte, 0xFFFFFFFFu));
   rel.wait = false;
   if (prebuilt) {
-    // ev_bbuilt[bi] was recorded after that build: the driver's wait orders it
+    // banks.ev_built[bi] was recorded after that build: the driver's wait orders it
   } else if (p.fz) {
     int p0 = 0, p1 = 1 << 30;
     if (band) band_planes(*band, p0, p1);
@@ -501,15 +477,7 @@ int build_chunk(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, int bi
       for (int l = 0; l < q.pd->nlevels; ++l)  // generic levels: planes
         if (copy_level(c, level_view(c->slot[kScratchSlot].lv[l]), K.lv[l], f, ps)) return -1;
     }
-    // whole frames: every row is valid.  The bank's last frame is the next
-    // chunk's previous pyramid (prev_level reads K.vlo / K.vhi); left at zero,
-    // or at an earlier fused build's band, the generic tracker's band test took
-    // every window of that pyramid for missing rows and wrote its escape flag,
-    // a null pointer in a call without bands
-    for (int l = 0; l < q.pd->nlevels; ++l) {
-      K.vlo[l] = 0;
-      K.vhi[l] = 1 << 30;
-    }
+    K.holds(kLayoutPlanes);  // whole frames: every row is valid
   }
   return 0;
 }
@@ -523,10 +491,10 @@ int build_chunk(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, int bi
 int launch_chunk(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, int bi, int j0, int F, TrkArgs &a,
                  TrkFramesArgs &b, TailRelease &rel, int f0 = 0) {
   const BandSpec *band = q.band;
-  const Bank &K = c->bank[bi];
+  const Bank &K = c->banks.bank[bi];
   for (int l = 0; l < q.pd->nlevels; ++l) {
     a.A[l] = prev_level(c, l);
-    a.B[l] = level_view(K.lv[l], f0, p.fz ? K.vlo[l] : 0, p.fz ? K.vhi[l] : (1 << 30));
+    a.B[l] = K.level(l, f0);
     b.lfs[l] = (long)K.lv[l].w * K.lv[l].h * (K.lv[l].il == kLayoutRec ? 3 : 1);
   }
   b.nframes = F;
@@ -546,7 +514,7 @@ int launch_chunk(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, int b
                                      q.fb_row0 + j0, count ? &rel : nullptr))
     return -1;
   HMARK_IN("track");
-  if (!p.serial && !p.ahead && c->prev.bank >= 0) HIPCHK(c, hipEventRecord(c->ev_bfree[c->prev.bank], c->stream));
+  if (!p.serial && !p.ahead && c->prev.bank >= 0) HIPCHK(c, hipEventRecord(c->banks.ev_free[c->prev.bank], c->stream));
   c->prev = PrevRef{bi, f0 + F - 1};
   return 0;
 }
@@ -556,113 +524,61 @@ int launch_chunk(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, int b
 int build_ahead(klt_hip_ctx *c, const FramesCall &q, const FramesPlan &p, const PstreamBehind &behind) {
   const BandSpec *band = q.band;
   if (!(band && band->next && band->next_n > 0 && p.fz)) return 0;
-  const int bj = c->bank_next;
+  const int bj = c->banks.peek();
   const int Fn = band->next_n < p.chunk ? band->next_n : p.chunk;
   if (c->ahead_ready) {  // with this chunk's tracker, so after the previous one: bank bj is free
     if (!behind.pwait) HIPCHK(c, hipStreamWaitEvent(c->pstream, c->ev_go, 0));
   } else {
-    HIPCHK(c, hipStreamWaitEvent(c->pstream, c->ev_bfree[bj], 0));
+    HIPCHK(c, hipStreamWaitEvent(c->pstream, c->banks.ev_free[bj], 0));
   }
   int p0 = 0, p1 = 1 << 30;
   band_planes(*band, p0, p1);
-  if (build_fused_bank(c, c->bank[bj], q.pd, band->next, q.pitch, q.stride, Fn, c->pstream, band->row_lo,
+  if (build_fused_bank(c, c->banks.bank[bj], q.pd, band->next, q.pitch, q.stride, Fn, c->pstream, band->row_lo,
                        band->row_hi, p0, p1, p.bil))
     return -1;
-  HIPCHK(c, hipEventRecord(c->ev_bbuilt[bj], c->pstream));
-  c->pre.bank = bj;
-  c->pre.src = band->next;
-  c->pre.F = Fn;
-  c->pre.stride = q.stride;
-  c->pre.row_lo = band->row_lo;
-  c->pre.row_hi = band->row_hi;
-  c->pre.il = p.bil;
+  HIPCHK(c, hipEventRecord(c->banks.ev_built[bj], c->pstream));
+  c->banks.built_ahead(BuiltAhead{bj, Fn, band->row_lo, band->row_hi, p.bil, band->next, q.stride});
   return 0;
 }
 
-// the next bank in turn; one built ahead for a band call is taken or overwritten
-int take_bank(klt_hip_ctx *c) {
-  const int bi = c->bank_next;
-  c->bank_next = (bi + 1) % 3;
-  if (c->pre.bank == bi) c->pre.bank = -1;
-  return bi;
-}
-
 // One replacement of lost features (klt_hip_set_frames_replace): the kept
-// pyramid is the frame just tracked, `row` its table row.  The list comes to
-// the host (pinned, x | y | val); `ahead` queues whatever does not depend on
-// it before the host waits.  With a lost slot, the frame's trackability map
-// is taken where the frame lies -- an image-only level 0 by k_min_eigen7_img
-// when the window and step are its own, anything else as
-// klt_hip_min_eigen_rows does it (which completes an image-only frame first)
-// -- and the selection engine fills the slots; the list and its table row go
-// back to the device.
+// pyramid is the frame just tracked, `row` its table row.  Its trackability
+// map is taken where the frame lies -- an image-only level 0 by
+// k_min_eigen7_img when the window and step are its own, anything else as
+// klt_hip_min_eigen_rows does it (which completes an image-only frame first).
+// The counters are the context's.
 template <class Ahead>
 int replace_lost(klt_hip_ctx *c, const FramesCall &q, long row, Ahead ahead) {
-  const int n = q.n;
-  if (n <= 0) return ahead();
-  hipStream_t st = c->stream;
-  if (ensure_rep_host(c, n, st)) return -1;
-  float *hx = c->h_rep, *hy = hx + n;
-  int *hv = reinterpret_cast<int *>(hy + n);
-  const size_t nb = sizeof(float) * (size_t)n;
-  HIPCHK(c, hipMemcpyAsync(hx, q.x, nb, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(hy, q.y, nb, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(hv, q.val, nb, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipEventRecord(c->ev_rep, st));
-  if (ahead()) return -1;
-  HIPCHK(c, hipEventSynchronize(c->ev_rep));
-  int lost = 0;
-  for (int k = 0; k < n; ++k) lost += hv[k] < 0;
-  if (!lost) return 0;  // KLTReplaceLostFeatures: nothing to replace
+  const int first[2] = {0, q.n};
+  const RepLists lists{1, q.n, first, q.x, q.y, q.val, q.tab_x, q.tab_y, q.tab_val, q.tab_stride};
   const klt_hip_select_desc &sd = c->rep.sel;
-  const TrkLevel L = prev_level(c, 0);
-  const int hw = sd.window_width / 2, hh = sd.window_height / 2, step = sd.nSkippedPixels + 1;
-  const int cx = L.w - 2 * sd.borderx, cy = L.h - 2 * sd.bordery;
-  int nx = cx > 0 ? (cx + step - 1) / step : 0, ny = cy > 0 ? (cy + step - 1) / step : 0;
-  if (grow(c, &c->d_rep_map, &c->rep_map_cap, (size_t)nx * ny)) return -1;
-  if ((long)nx * ny > 0) {
-    const bool img7 = L.il == kLayoutImg && hw == kRG && hh == kRG && step <= 2 && c->lazy_gg.w == 2 * kRG + 1 &&
-                      c->lazy_gd.w == 2 * kRG + 1;
-    if (img7) {
+  const auto maps = [&](const EigMultiArgs &, const SelGrid &g) -> long {
+    const TrkLevel L = prev_level(c, 0);
+    const long np = (long)g.nx * g.ny;
+    if (L.il == kLayoutImg && g.hw == kRG && g.hh == kRG && g.step <= 2 && c->lazy_gg.w == 2 * kRG + 1 &&
+        c->lazy_gd.w == 2 * kRG + 1) {
       GradTaps t;
       for (int m = 0; m < 2 * kRG + 1; ++m) {
         t.g[m] = c->lazy_gg.k[m];
         t.d[m] = c->lazy_gd.k[m];
       }
-      TimedScope ts(c, T_EIG, st);
-      if (launched(c, "k_min_eigen7_img", launch_min_eigen_img(st, L.img, L.w, L.h, t, sd.borderx, sd.bordery, step, nx,
-                                                               ny, c->d_rep_map, &c->eig_kernel)))
-        return -1;
-    } else {
-      int r0 = 0, r1 = 0;
-      const int rc = klt_hip_min_eigen_rows(c, &sd, 0, L.h, c->d_rep_map, &nx, &ny, &r0, &r1);
-      if (rc < 0) return -1;
-      if (rc > 0 || r0 != 0 || r1 != ny) return fail(c, "track_frames: the tracked frame does not hold every row of the map");
+      TimedScope ts(c, T_EIG, c->stream);
+      return launched(c, "k_min_eigen7_img", launch_min_eigen_img(c->stream, L.img, L.w, L.h, t, sd.borderx, sd.bordery,
+                                                                  g.step, g.nx, g.ny, c->d_rep_map, &c->eig_kernel))
+                 ? -1 : np;
     }
-  }
-  std::vector<unsigned char> changed((size_t)n, 0);
-  if (klt_hip_select_dev_map(c, c->d_rep_map, nx, ny, &sd, L.w, L.h, c->rep.mindist, c->rep.min_eigenvalue, 0, hx, hy,
-                             hv, changed.data(), n))
+    int nx = 0, ny = 0, r0 = 0, r1 = 0;
+    const int rc = klt_hip_min_eigen_rows(c, &sd, 0, L.h, c->d_rep_map, &nx, &ny, &r0, &r1);
+    if (rc < 0) return -1;
+    if (rc > 0 || r0 != 0 || r1 != ny) return fail(c, "track_frames: the tracked frame does not hold every row of the map");
+    return np;
+  };
+  if (c->rep_changed.size() < (size_t)q.n) c->rep_changed.resize((size_t)q.n, 0);
+  const TrkLevel L = prev_level(c, 0);
+  long filled = 0;
+  if (replace_step(c, lists, c->rep, L.w, L.h, row, RepCounters{c->rep_changed.data(), &c->rep_runs, &c->rep_filled},
+                   ahead, maps, &filled))
     return -1;
-  if (c->rep_changed.size() < (size_t)n) c->rep_changed.resize((size_t)n, 0);
-  long filled = 0, written = 0;
-  for (int k = 0; k < n; ++k) {
-    if (!changed[k]) continue;
-    c->rep_changed[k] = 1;
-    ++written;
-    filled += hv[k] >= 0;
-  }
-  ++c->rep_runs;
-  c->rep_filled += filled;
-  if (!written) return 0;
-  HIPCHK(c, hipMemcpyAsync(q.x, hx, nb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(q.y, hy, nb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(q.val, hv, nb, hipMemcpyHostToDevice, st));
-  if (q.tab_x) {  // the row carries the list after the replacement
-    HIPCHK(c, hipMemcpyAsync(q.tab_x + row * q.tab_stride, q.x, nb, hipMemcpyDeviceToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(q.tab_y + row * q.tab_stride, q.y, nb, hipMemcpyDeviceToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(q.tab_val + row * q.tab_stride, q.val, nb, hipMemcpyDeviceToDevice, st));
-  }
   // results never depend on the cached processing order, but new features
   // would sit in the lost features' places
   if (filled) c->perm_n = -1;
@@ -684,14 +600,13 @@ int track_frames_replacing(klt_hip_ctx *c, const FramesCall &q, const FramesPlan
     if (ahead_bank >= 0) {
       bi = ahead_bank;
     } else {
-      bi = take_bank(c);
+      bi = c->banks.take();
       if (build_chunk(c, q, p, bi, F, q.frames + (long)j0 * q.stride, c->stream, false, behind, rel)) return -1;
     }
     ahead_bank = -1;
     const int jn = j0 + F, Fn = p.F < q.nframes - jn ? p.F : q.nframes - jn;
     for (int f0 = 0; f0 < F;) {
-      const long due = every - c->rep_frames % every;  // frames up to the next replacement
-      const int f1 = f0 + due < F ? (int)(f0 + due) : F;
+      const int f1 = next_cut(c->rep_frames, every, f0, F);
       TrkFramesArgs b;
       memset(&b, 0, sizeof b);
       if (q.n > 0 && order_features(c, c->stream, q.pd->nrows, q.y, q.val, q.n, f1 - f0, nullptr, b)) return -1;
@@ -700,7 +615,7 @@ int track_frames_replacing(klt_hip_ctx *c, const FramesCall &q, const FramesPlan
       if (c->rep_frames % every == 0) {
         const auto ahead = [&]() -> int {
           if (f1 < F || Fn <= 0) return 0;
-          ahead_bank = take_bank(c);
+          ahead_bank = c->banks.take();
           return build_chunk(c, q, p, ahead_bank, Fn, q.frames + (long)jn * q.stride, c->stream, false, behind, rel);
         };
         if (replace_lost(c, q, j0 + f1 - 1, ahead)) return -1;
@@ -729,10 +644,10 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
   FramesPlan p = plan_layout(c, q);
   if (!p.lazy && prev_full(c)) return -1;
   if (ensure_pipeline(c)) return -1;
-  if (!c->ev_bbuilt[0])
+  if (!c->banks.ev_built[0])
     for (int k = 0; k < 3; ++k) {
-      HIPCHK(c, hipEventCreateWithFlags(&c->ev_bbuilt[k], hipEventDisableTiming));
-      HIPCHK(c, hipEventCreateWithFlags(&c->ev_bfree[k], hipEventDisableTiming));
+      HIPCHK(c, hipEventCreateWithFlags(&c->banks.ev_built[k], hipEventDisableTiming));
+      HIPCHK(c, hipEventCreateWithFlags(&c->banks.ev_free[k], hipEventDisableTiming));
     }
   if (plan_frames(c, q, chunk, p)) return -1;
   HMARK("budget");
@@ -756,8 +671,7 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
   if (c->rep_on) return track_frames_replacing(c, q, p, a, behind);
   TailRelease rel{p.tail_left, false, 0};
   for (int j0 = 0; j0 < nframes; j0 += p.F) {
-    const int F = p.F < nframes - j0 ? p.F : nframes - j0, bi = c->bank_next;
-    c->bank_next = (bi + 1) % 3;
+    const int F = p.F < nframes - j0 ? p.F : nframes - j0;
     const unsigned char *src = frames + (long)j0 * stride;
     // overlapped: the pyramid stream builds chunk c+1 while chunk c is tracked;
     // serial: both on the tracking stream (no two kernels share the CUs)
@@ -770,15 +684,15 @@ int track_frames_impl(klt_hip_ctx *c, const klt_hip_pyr_desc *pd, const klt_hip_
     HMARK("chunk_top");
     if (n > 0 && order_features(c, c->stream, pd->nrows, y, val, n, F, band ? band->own : nullptr, b)) return -1;
     HMARK("order");
-    const bool prebuilt = band && c->pre.bank == bi && c->pre.src == src && c->pre.F == F &&
-                          c->pre.stride == stride && c->pre.row_lo == band->row_lo &&
-                          c->pre.row_hi == band->row_hi && c->pre.il == p.bil;
-    if (c->pre.bank == bi) c->pre.bank = -1;  // taken now, or about to be overwritten
+    // a band call takes the bank the previous call built ahead, when it holds these frames
+    const BuiltAhead want{-1, F, band ? band->row_lo : 0, band ? band->row_hi : 0, p.bil, src, stride};
+    bool prebuilt = false;
+    const int bi = c->banks.take(band ? &want : nullptr, &prebuilt);
     if (build_chunk(c, q, p, bi, F, src, ps, prebuilt, behind, rel)) return -1;
     HMARK("pyramids");
     if (!p.serial) {  // the built bank to the tracking stream
-      if (!prebuilt) HIPCHK(c, hipEventRecord(c->ev_bbuilt[bi], ps));
-      HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_bbuilt[bi], 0));
+      if (!prebuilt) HIPCHK(c, hipEventRecord(c->banks.ev_built[bi], ps));
+      HIPCHK(c, hipStreamWaitEvent(c->stream, c->banks.ev_built[bi], 0));
     }
     if (launch_chunk(c, q, p, bi, j0, F, a, b, rel)) return -1;
   }
@@ -1047,17 +961,13 @@ KLT_API int klt_hip_min_eigen_rows(klt_hip_ctx *c, const klt_hip_select_desc *d,
                                    int *dev_map, int *nx, int *ny, int *r0, int *r1) {
   if (!c || !d || !nx || !ny || !r0 || !r1) return fail(c, "min_eigen_rows: null argument");
   if (!c->frames_ready) return fail(c, "min_eigen_rows: no tracked frame (call klt_hip_frames_begin)");
-  if (c->prev.bank >= 0 && c->bank[c->prev.bank].lv[0].il == kLayoutImg && (use_device(c) || prev_full(c)))
-    return -1;  // the map reads level-0 gradients
+  if (kept_image_only(c) && (use_device(c) || prev_full(c))) return -1;  // the map reads level-0 gradients
   const TrkLevel L = prev_level(c, 0);
-  const int hw = d->window_width / 2, hh = d->window_height / 2;
-  const int step = d->nSkippedPixels + 1;
+  const SelGrid g = sel_grid(*d, L.w, L.h);
+  const int hw = g.hw, hh = g.hh, step = g.step, gx = g.nx, gy = g.ny;
   if (step < 1) return fail(c, "min_eigen_rows: bad nSkippedPixels");
   const int bx = d->borderx, by = d->bordery;
   if (bx < hw || by < hh) return fail(c, "min_eigen_rows: border smaller than window half size");
-  const int cx = L.w - 2 * bx, cy = L.h - 2 * by;
-  const int gx = cx > 0 ? (cx + step - 1) / step : 0;
-  const int gy = cy > 0 ? (cy + step - 1) / step : 0;
   // grid rows j with by + j*step in [row_lo, row_hi)
   auto first_at = [&](int y) { return clampi(y <= by ? 0 : (y - by + step - 1) / step, 0, gy); };
   const int j0 = first_at(row_lo), j1 = first_at(row_hi) > j0 ? first_at(row_hi) : j0;
@@ -1083,13 +993,12 @@ extern "C" void klt_default_grad_taps(klt_hip_taps *gauss, klt_hip_taps *deriv);
 KLT_API int klt_hip_min_eigen_plane(klt_hip_ctx *c, const float *dev_img, int ncols, int nrows,
                                     const klt_hip_select_desc *d, int *dev_map) {
   if (!c || !dev_img || !d || !dev_map || ncols < 1 || nrows < 1) return fail(c, "min_eigen_plane: bad argument");
-  const int step = d->nSkippedPixels + 1;
+  const SelGrid g = sel_grid(*d, ncols, nrows);
+  const int step = g.step, nx = g.nx, ny = g.ny;
   if (d->window_width != 2 * kRG + 1 || d->window_height != 2 * kRG + 1)
     return fail(c, "min_eigen_plane: window %dx%d, the kernel covers 7x7 only", d->window_width, d->window_height);
   if (step < 1 || step > 2) return fail(c, "min_eigen_plane: step %d, the kernel covers 1 and 2", step);
   if (d->borderx < kRG || d->bordery < kRG) return fail(c, "min_eigen_plane: border smaller than window half size");
-  const int cx = ncols - 2 * d->borderx, cy = nrows - 2 * d->bordery;
-  const int nx = cx > 0 ? (cx + step - 1) / step : 0, ny = cy > 0 ? (cy + step - 1) / step : 0;
   if ((long)nx * ny == 0) return 0;
   if (use_device(c)) return -1;
   klt_hip_taps gg, gd;

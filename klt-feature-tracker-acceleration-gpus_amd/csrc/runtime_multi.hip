@@ -22,7 +22,7 @@
 // one k_min_eigen7_multi launch over the adjacent pyramids of that frame, and
 // the selection engine fills each one's slots from its own map, one sequence
 // after the other.
-#include "runtime.h"
+#include "replace_step.h"
 
 namespace {
 // what the multi instances cover: the default configuration
@@ -53,109 +53,32 @@ struct MultiReplace {
   long *runs, *filled;
 };
 
-struct MultiCall {
-  const klt_hip_pyr_desc *pd;
-  int nseq, n;
-  const TrkMultiArgs *ms;
-  float *x, *y;
-  int *val;
-  float *tab_x, *tab_y;
-  int *tab_val;
-  long tab_stride;
-};
-
-// n features of x | y | val between the device lists and the pinned block:
-// one transfer where the caller keeps the three arrays in one block
-int move_lists(klt_hip_ctx *c, const MultiCall &q, float *h, hipMemcpyKind kind, hipStream_t st) {
-  const size_t nb = sizeof(float) * (size_t)q.n;
-  const bool down = kind == hipMemcpyDeviceToHost;
-  if (q.y == q.x + q.n && reinterpret_cast<float *>(q.val) == q.y + q.n) {
-    HIPCHK(c, hipMemcpyAsync(down ? (void *)h : (void *)q.x, down ? (const void *)q.x : (const void *)h, 3 * nb, kind, st));
-    return 0;
-  }
-  void *dev[3] = {q.x, q.y, q.val};
-  for (int k = 0; k < 3; ++k) {
-    float *hk = h + (size_t)k * q.n;
-    HIPCHK(c, hipMemcpyAsync(down ? (void *)hk : dev[k], down ? (const void *)dev[k] : (const void *)hk, nb, kind, st));
-  }
-  return 0;
-}
-
-// One replacement for every sequence (KLTReplaceLostFeatures in sequential
-// mode, each on its own list and its own frame): the frame just tracked is
-// group `group` of bank K, `row` its table row.  `ahead` queues whatever does
-// not depend on the lists before the host waits for them.
+// One replacement for every sequence: the frame just tracked is group `group`
+// of bank K, whose nseq adjacent pyramids one k_min_eigen7_multi launch reads
+// (a description with another window or step: a launch per sequence)
 template <class Ahead>
-int replace_lost_multi(klt_hip_ctx *c, const MultiCall &q, const MultiReplace &r, const Bank &K, long group, long row,
+int replace_lost_multi(klt_hip_ctx *c, const RepLists &q, const MultiReplace &r, const Bank &K, long group, long row,
                        Ahead ahead) {
-  const int n = q.n;
-  if (n <= 0) return ahead();
-  hipStream_t st = c->stream;
-  if (ensure_rep_host(c, n, st)) return -1;
-  float *hx = c->h_rep, *hy = hx + n;
-  int *hv = reinterpret_cast<int *>(hy + n);
-  if (move_lists(c, q, hx, hipMemcpyDeviceToHost, st)) return -1;
-  HIPCHK(c, hipEventRecord(c->ev_rep, st));
-  if (ahead()) return -1;
-  HIPCHK(c, hipEventSynchronize(c->ev_rep));
-  // the sequences with a lost slot: the others are left alone
-  EigMultiArgs m;
-  memset(&m, 0, sizeof m);
-  for (int s = 0; s < q.nseq; ++s) {
-    int lost = 0;
-    for (int k = q.ms->first[s]; k < q.ms->first[s + 1]; ++k) lost += hv[k] < 0;
-    if (lost) m.seq[m.nsel++] = s;
-  }
-  if (!m.nsel) return 0;
-  const klt_hip_select_desc &sd = r.d->sel;
   const Level &L0 = K.lv[0];
-  const int hw = sd.window_width / 2, hh = sd.window_height / 2, step = sd.nSkippedPixels + 1;
-  const int cx = L0.w - 2 * sd.borderx, cy = L0.h - 2 * sd.bordery;
-  const int nx = cx > 0 ? (cx + step - 1) / step : 0, ny = cy > 0 ? (cy + step - 1) / step : 0;
-  const long np = (long)nx * ny, lfs = (long)L0.w * L0.h * kRec;
-  if (grow(c, &c->d_rep_map, &c->rep_map_cap, (size_t)(np * m.nsel))) return -1;
-  if (np > 0) {
-    const float *rec = L0.img + group * q.nseq * lfs;  // the frame's nseq adjacent pyramids
+  const klt_hip_select_desc &sd = r.d->sel;
+  const auto maps = [&](const EigMultiArgs &m, const SelGrid &g) -> long {
+    const long np = (long)g.nx * g.ny, lfs = (long)L0.w * L0.h * kRec;
+    const float *rec = L0.img + group * q.nseq * lfs;
+    hipStream_t st = c->stream;
     TimedScope ts(c, T_EIG, st);
-    if (hw == kRG && hh == kRG && step <= 2) {
-      if (launched(c, "k_min_eigen7_multi", launch_min_eigen_multi(st, rec, lfs, m, L0.w, sd.borderx, sd.bordery, step, nx,
-                                                                   ny, c->d_rep_map, &c->eig_kernel)))
+    if (g.hw == kRG && g.hh == kRG && g.step <= 2)
+      return launched(c, "k_min_eigen7_multi", launch_min_eigen_multi(st, rec, lfs, m, L0.w, sd.borderx, sd.bordery, g.step,
+                                                                      g.nx, g.ny, c->d_rep_map, &c->eig_kernel))
+                 ? -1 : np;
+    for (int i = 0; i < m.nsel; ++i) {
+      const float *f = rec + m.seq[i] * lfs;
+      if (launched(c, "k_min_eigen", launch_min_eigen(st, f + kRecGx, f + kRecGy, L0.w, kRec, sd.borderx, sd.bordery, g.step,
+                                                      g.nx, g.ny, g.hw, g.hh, c->d_rep_map + i * np, &c->eig_kernel)))
         return -1;
-    } else {  // not with the window the call covers; any other description: a launch per sequence
-      for (int i = 0; i < m.nsel; ++i) {
-        const float *g = rec + m.seq[i] * lfs;
-        if (launched(c, "k_min_eigen", launch_min_eigen(st, g + kRecGx, g + kRecGy, L0.w, kRec, sd.borderx, sd.bordery, step,
-                                                        nx, ny, hw, hh, c->d_rep_map + i * np, &c->eig_kernel)))
-          return -1;
-      }
     }
-  }
-  std::vector<unsigned char> changed((size_t)n, 0);
-  long written = 0;
-  for (int i = 0; i < m.nsel; ++i) {
-    const int s = m.seq[i], a = q.ms->first[s], ns = q.ms->first[s + 1] - a;
-    if (klt_hip_select_dev_map(c, c->d_rep_map + i * np, nx, ny, &sd, L0.w, L0.h, r.d->mindist, r.d->min_eigenvalue, 0,
-                               hx + a, hy + a, hv + a, changed.data() + a, ns))
-      return -1;
-    long filled = 0;
-    for (int k = a; k < a + ns; ++k) {
-      if (!changed[k]) continue;
-      if (r.changed) r.changed[k] |= 1;
-      ++written;
-      filled += hv[k] >= 0;
-    }
-    if (r.runs) ++r.runs[s];
-    if (r.filled) r.filled[s] += filled;
-  }
-  if (!written) return 0;
-  if (move_lists(c, q, hx, hipMemcpyHostToDevice, st)) return -1;
-  if (q.tab_x) {  // the row carries every list after the replacement
-    const size_t nb = sizeof(float) * (size_t)n;
-    HIPCHK(c, hipMemcpyAsync(q.tab_x + row * q.tab_stride, q.x, nb, hipMemcpyDeviceToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(q.tab_y + row * q.tab_stride, q.y, nb, hipMemcpyDeviceToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(q.tab_val + row * q.tab_stride, q.val, nb, hipMemcpyDeviceToDevice, st));
-  }
-  return 0;
+    return np;
+  };
+  return replace_step(c, q, *r.d, L0.w, L0.h, row, RepCounters{r.changed, r.runs, r.filled}, ahead, maps);
 }
 
 // both calls; rep == nullptr: klt_hip_track_frames_multi
@@ -189,11 +112,7 @@ int track_multi(klt_hip_ctx *c, const char *who, const klt_hip_pyr_desc *pd, con
   const int n = (int)total;
   if (!frames) return fail(c, "%s: null frames", who);
   if (n > 0 && (!x || !y || !val)) return fail(c, "%s: null feature arrays", who);
-  const int ntab = (tab_x != nullptr) + (tab_y != nullptr) + (tab_val != nullptr);
-  if (ntab != 0 && ntab != 3) return fail(c, "%s: give all three table arrays or none", who);
-  if (ntab && tab_stride < n) return fail(c, "%s: table stride %ld < n %d", who, tab_stride, n);
-  if (pitch < (long)pd->ncols * frame_bpp(c->frame_format))
-    return fail(c, "%s: pitch %ld < ncols %d * %d bytes per pixel", who, pitch, pd->ncols, frame_bpp(c->frame_format));
+  if (tables_refused(c, who, tab_x, tab_y, tab_val, tab_stride, n, pitch, pd->ncols)) return -1;
   if (multi_refused(c, pd, td, who)) return -1;
   if (nframes == 0) return 0;
   if (use_device(c)) return -1;
@@ -207,17 +126,9 @@ int track_multi(klt_hip_ctx *c, const char *who, const klt_hip_pyr_desc *pd, con
   const int F0 = chunk < nframes ? chunk : nframes;
 
   // from here on the context has no current pyramid: the banks are this call's
-  c->frames_ready = false;
-  c->prev = PrevRef{};
-  if (c->pstream && c->pre.bank >= 0) HIPCHK(c, hipStreamSynchronize(c->pstream));  // a band call's build-ahead
-  c->pre.bank = -1;
+  if (forget_kept(c)) return -1;
   c->chunk_used = chunk;
-  const int P = nseq * chunk;  // pyramids per bank
-  if (!(bank_fits(c->bank[0], pd, P) && bank_fits(c->bank[1], pd, P) && bank_fits(c->bank[2], pd, P))) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->pstream) HIPCHK(c, hipStreamSynchronize(c->pstream));
-    if (ensure_banks(c, pd, P)) return -1;
-  }
+  if (ensure_banks(c, pd, nseq * chunk)) return -1;  // pyramids per bank
 
   TrkArgs a;
   fill_trk_args(td, pd->nlevels, pd->nlevels > 1 ? pd->subsampling : 1, pd->ncols, pd->nrows, a);
@@ -226,7 +137,7 @@ int track_multi(klt_hip_ctx *c, const char *who, const klt_hip_pyr_desc *pd, con
   a.aos = 1;
   hipStream_t st = c->stream;
   const bool frame_major = stride == (long)nseq * seq_stride;
-  const MultiCall q{pd, nseq, n, &ms, x, y, val, tab_x, tab_y, tab_val, tab_stride};
+  const RepLists q{nseq, n, ms.first, x, y, val, tab_x, tab_y, tab_val, tab_stride};
 
   // a chunk's pyramids: F frames of every sequence from call frame j0 + 1 into bank K
   const auto build = [&](Bank &K, int j0, int F) -> int {
@@ -241,30 +152,26 @@ int track_multi(klt_hip_ctx *c, const char *who, const klt_hip_pyr_desc *pd, con
   };
 
   // the start images' group: pyramids 0 .. nseq-1 of a bank
-  int bi = c->bank_next;
-  if (build_fused_bank(c, c->bank[bi], pd, frames, pitch, seq_stride, nseq, st, 0, 1 << 30, 0, 1 << 30, kLayoutRec))
+  int bi = c->banks.take();
+  if (build_fused_bank(c, c->banks.bank[bi], pd, frames, pitch, seq_stride, nseq, st, 0, 1 << 30, 0, 1 << 30, kLayoutRec))
     return -1;
   long prev_first = 0;  // the group this chunk starts from: pyramids prev_first .. +nseq of bank bi
-  bool built = false;   // this chunk's pyramids were queued at the previous chunk's last cut
+  int ahead_bank = -1;  // >= 0: this chunk's pyramids were queued there at the previous chunk's last cut
   for (int j0 = 0; j0 < nframes; j0 += F0) {
     const int F = F0 < nframes - j0 ? F0 : nframes - j0, pb = bi;
-    bi = (bi + 1) % 3;
-    Bank &K = c->bank[bi];
-    if (!built && build(K, j0, F)) return -1;
-    built = false;
+    bi = ahead_bank >= 0 ? ahead_bank : c->banks.take();
+    Bank &K = c->banks.bank[bi];
+    if (ahead_bank < 0 && build(K, j0, F)) return -1;
+    ahead_bank = -1;
     const int jn = j0 + F, Fn = F0 < nframes - jn ? F0 : nframes - jn;
     for (int f0 = 0; f0 < F;) {
       // up to the next frame at which a replacement is due
-      int f1 = F;
-      if (rep) {
-        const long due = rep->d->every - (rep->count0 + j0 + f0) % rep->d->every;
-        if (f0 + due < F) f1 = (int)(f0 + due);
-      }
+      const int f1 = rep ? next_cut(rep->count0 + j0 + f0, rep->d->every, f0, F) : F;
       TrkFramesArgs b;
       memset(&b, 0, sizeof b);
       for (int l = 0; l < pd->nlevels; ++l) {
-        a.A[l] = f0 ? level_view(K.lv[l], (long)(f0 - 1) * nseq) : level_view(c->bank[pb].lv[l], prev_first);
-        a.B[l] = level_view(K.lv[l], (long)f0 * nseq);
+        a.A[l] = f0 ? K.level(l, (long)(f0 - 1) * nseq) : c->banks.bank[pb].level(l, prev_first);
+        a.B[l] = K.level(l, (long)f0 * nseq);
         b.lfs[l] = (long)K.lv[l].w * K.lv[l].h * 3;
       }
       b.nframes = f1 - f0;
@@ -282,8 +189,8 @@ int track_multi(klt_hip_ctx *c, const char *who, const klt_hip_pyr_desc *pd, con
       if (rep && (rep->count0 + j0 + f1) % rep->d->every == 0) {
         const auto ahead = [&]() -> int {
           if (f1 < F || Fn <= 0) return 0;
-          built = true;
-          return build(c->bank[(bi + 1) % 3], jn, Fn);
+          ahead_bank = c->banks.take();
+          return build(c->banks.bank[ahead_bank], jn, Fn);
         };
         if (replace_lost_multi(c, q, *rep, K, f1 - 1, j0 + f1 - 1, ahead)) return -1;
       }
@@ -291,7 +198,6 @@ int track_multi(klt_hip_ctx *c, const char *who, const klt_hip_pyr_desc *pd, con
     }
     prev_first = (long)(F - 1) * nseq;
   }
-  c->bank_next = (bi + 1) % 3;
   return 0;
 }
 }  // namespace
@@ -328,7 +234,8 @@ KLT_API int klt_hip_min_eigen_records(klt_hip_ctx *c, const float *dev_rec, long
   if (!c || !dev_rec || !which || !d || !dev_maps || ncols < 1 || nrows < 1)
     return fail(c, "min_eigen_records: bad argument");
   if (nsel < 1 || nsel > kMaxSeq) return fail(c, "min_eigen_records: nsel %d is not in 1..%d", nsel, kMaxSeq);
-  const int step = d->nSkippedPixels + 1;
+  const SelGrid g = sel_grid(*d, ncols, nrows);
+  const int step = g.step, nx = g.nx, ny = g.ny;
   if (d->window_width != 2 * kRG + 1 || d->window_height != 2 * kRG + 1)
     return fail(c, "min_eigen_records: window %dx%d, the kernel covers 7x7 only", d->window_width, d->window_height);
   if (step < 1 || step > 2) return fail(c, "min_eigen_records: step %d, the kernel covers 1 and 2", step);
@@ -341,8 +248,6 @@ KLT_API int klt_hip_min_eigen_records(klt_hip_ctx *c, const float *dev_rec, long
     if (which[i] < 0) return fail(c, "min_eigen_records: frame index %d", which[i]);
     m.seq[i] = which[i];
   }
-  const int cx = ncols - 2 * d->borderx, cy = nrows - 2 * d->bordery;
-  const int nx = cx > 0 ? (cx + step - 1) / step : 0, ny = cy > 0 ? (cy + step - 1) / step : 0;
   if ((long)nx * ny == 0) return 0;
   if (use_device(c)) return -1;
   {

@@ -203,20 +203,21 @@ size_t env_size(const char *name, size_t dflt) {
 }  // namespace
 
 void free_banks(klt_hip_ctx *c) {
-  for (auto &K : c->bank) {
+  BankRing &R = c->banks;
+  for (auto &K : R.bank) {
     for (auto &L : K.lv) {
-      if (!c->bank_arena) hipFree(L.img);  // one block per level
+      if (!R.arena) hipFree(L.img);  // one block per level
       L.img = L.gx = L.gy = nullptr;
       L.cap = 0;
     }
-    if (!c->bank_arena) hipFree(K.hs);
+    if (!R.arena) hipFree(K.hs);
     K.hs = nullptr;
     K.hs_cap = 0;
     K.frames = 0;
   }
-  hipFree(c->bank_arena);
-  c->bank_arena = nullptr;
-  c->bank_arena_bytes = 0;
+  hipFree(R.arena);
+  R.arena = nullptr;
+  R.arena_bytes = 0;
 }
 
 // Default bank budget: a quarter of the device's memory, at most 64 GiB --
@@ -244,21 +245,47 @@ int budget_chunk(klt_hip_ctx *c, const klt_hip_pyr_desc *d) {
   return lo;
 }
 
-// (re)lay out the three banks for `frames` pyramids shaped like desc d.  The
-// caller has drained both streams.
+// all three banks hold `frames` pyramids shaped like desc d
+bool banks_fit(const klt_hip_ctx *c, const klt_hip_pyr_desc *d, int frames) {
+  for (const Bank &K : c->banks.bank) {
+    if (K.nlev != d->nlevels) return false;
+    // the level sizes below follow the bank's own subsampling: a bank laid out
+    // for another one (a context reused for a pyramid of the same depth) does
+    // not fit, whatever its first level's size
+    if (K.ss != (d->nlevels > 1 ? d->subsampling : 1)) return false;
+    int w = d->ncols, h = d->nrows;
+    for (int l = 0; l < d->nlevels; ++l) {
+      const Level &L = K.lv[l];
+      if (L.w != w || L.h != h || !L.img || L.cap < (size_t)(w > 0 ? w : 1) * (h > 0 ? h : 1) * frames) return false;
+      w /= K.ss;
+      h /= K.ss;
+    }
+    if (d->nlevels == 2 && K.hs_cap < (size_t)(K.lv[1].w > 0 ? K.lv[1].w : 1) * d->nrows * frames) return false;
+  }
+  return true;
+}
+
+// The three banks for `frames` pyramids shaped like desc d.  Banks that do not
+// fit are laid out again with both streams drained, and a build-ahead record
+// goes with the old layout; a kept pyramid living in a bank is the caller's to
+// move out first.
 int ensure_banks(klt_hip_ctx *c, const klt_hip_pyr_desc *d, int frames) {
+  if (banks_fit(c, d, frames)) return 0;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->pstream) HIPCHK(c, hipStreamSynchronize(c->pstream));
+  c->banks.drop_ahead();
   const bool arena = env_size("KLT_BANK_ARENA", 1) != 0;  // 0: the old per-plane allocations (A/B only)
   const size_t need = bank_arena_bytes(d, frames);
-  if (!arena || need > c->bank_arena_bytes || !c->bank_arena) free_banks(c);
+  if (!arena || need > c->banks.arena_bytes || !c->banks.arena) free_banks(c);
   if (!arena) {  // one allocation per plane (the round-1/2 layout; experiments only)
-    for (auto &K : c->bank) {
+    for (auto &K : c->banks.bank) {
       for (int l = 0; l < d->nlevels; ++l) {
         const size_t n = bank_plane_floats(d, l, frames);
         HIPCHK(c, hipMalloc((void **)&K.lv[l].img, 3 * n * sizeof(float)));
       }
       if (d->nlevels == 2) HIPCHK(c, hipMalloc((void **)&K.hs, bank_hs_floats(d, frames) * sizeof(float)));
     }
-  } else if (!c->bank_arena) {
+  } else if (!c->banks.arena) {
     size_t fr = 0, tot = 0;
     HIPCHK(c, hipMemGetInfo(&fr, &tot));
     if (need > fr)
@@ -266,21 +293,21 @@ int ensure_banks(klt_hip_ctx *c, const klt_hip_pyr_desc *d, int frames) {
                   frames, d->ncols, d->nrows, need, fr);
     // physically contiguous when the driver can (experiment hook KLT_BANK_CONTIG=1)
     if (!(env_size("KLT_BANK_CONTIG", 0) &&
-          hipExtMallocWithFlags(&c->bank_arena, need, hipDeviceMallocContiguous) == hipSuccess)) {
+          hipExtMallocWithFlags(&c->banks.arena, need, hipDeviceMallocContiguous) == hipSuccess)) {
       (void)hipGetLastError();
-      c->bank_arena = nullptr;
-      HIPCHK(c, hipMalloc(&c->bank_arena, need));
+      c->banks.arena = nullptr;
+      HIPCHK(c, hipMalloc(&c->banks.arena, need));
     }
-    c->bank_arena_bytes = need;
+    c->banks.arena_bytes = need;
   }
   size_t off = 0;
   auto take = [&](size_t floats) {
     off = (off + kPlaneAlign - 1) / kPlaneAlign * kPlaneAlign;
-    float *p = reinterpret_cast<float *>(static_cast<char *>(c->bank_arena) + off);
+    float *p = reinterpret_cast<float *>(static_cast<char *>(c->banks.arena) + off);
     off += floats * sizeof(float);
     return p;
   };
-  for (auto &K : c->bank) {
+  for (auto &K : c->banks.bank) {
     int w = d->ncols, h = d->nrows;
     K.nlev = d->nlevels;
     K.ss = d->nlevels > 1 ? d->subsampling : 1;
@@ -307,7 +334,7 @@ int ensure_banks(klt_hip_ctx *c, const klt_hip_pyr_desc *d, int frames) {
 // fused pyramids of F frames (src + f*stride) into bank K, two launches.
 // Level-0 rows [row_lo, row_hi) are built (whole 32-row tiles, global
 // coordinates, so every built value is the full-frame value) and the level-1
-// tiles whose sigma-3.6 inputs lie inside them; K.vlo/vhi record what is valid.
+// tiles whose sigma-3.6 inputs lie inside them; K.holds records what is valid.
 // row_lo/row_hi: the level-0 rows to build (the sigma-3.6 rows pass hs over
 // all of them); plane_lo/plane_hi: the rows whose level-0 planes are stored
 // (a band's outer margin feeds only level 1)
@@ -321,7 +348,10 @@ int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const u
   const DefTaps T = default_taps(d);
   const bool two = d->nlevels == 2;
   const int W1 = two ? K.lv[1].w : 0, H1 = two ? K.lv[1].h : 0;
-  if ((long)W * H == 0 || F <= 0) return 0;
+  if ((long)W * H == 0 || F <= 0) {
+    K.holds(il);
+    return 0;
+  }
   const int vec_u8 = vec_u8_ok(src, pitch, stride, W);
   const int vec_out = (W % 4 == 0) ? 1 : 0;
   const long fs0 = (long)W * H, fsh = hs_size(W1, H), fs1 = (long)W1 * H1;
@@ -333,7 +363,8 @@ int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const u
   // levels above interleaved
   const int il1 = il == kLayoutImg ? kLayoutRec : il;
   const int np0 = il == kLayoutRec ? 3 : 1, np = il1 ? 3 : 1;
-  for (int l = 0; l < d->nlevels; ++l) K.lv[l].il = l == 0 ? il : il1;
+  int lo[KLT_HIP_MAX_LEVELS] = {}, hi[KLT_HIP_MAX_LEVELS];  // valid rows per level: whole frames unless set below
+  for (int &v : hi) v = 1 << 30;
   {
     TimedScope ts(c, T_L0, st, F);
     const long o0 = first * np0 * fs0;
@@ -342,8 +373,8 @@ int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const u
                   r1, &p0, &p1, il, c->frame_format))
       return -1;
   }
-  K.vlo[0] = p0;
-  K.vhi[0] = p1 >= H ? (1 << 30) : p1;
+  lo[0] = p0;
+  hi[0] = p1 >= H ? (1 << 30) : p1;
   if (two && (long)W1 * H1 > 0) {
     // level-1 row Y (img1 and its gradients) reads hs rows 4Y-20 .. 4Y+24:
     // it is exact when those lie inside the built level-0 rows (or past an
@@ -354,8 +385,8 @@ int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const u
     const int nt1 = (H1 + TH1 - 1) / TH1;
     const int ylo = r0 == 0 ? 0 : (r0 + 20 + 3) / 4;
     const int yhi = r1 >= H ? H1 : (r1 >= 25 ? (r1 - 25) / 4 + 1 : 0);
-    K.vlo[1] = ylo;
-    K.vhi[1] = yhi >= H1 ? (1 << 30) : yhi;
+    lo[1] = ylo;
+    hi[1] = yhi >= H1 ? (1 << 30) : yhi;
     if (yhi > ylo) {
       const int t1lo = ylo / TH1, t1hi = clampi((yhi + TH1 - 1) / TH1, t1lo, nt1);
       HMARK_IN("l0_launched");
@@ -369,6 +400,7 @@ int build_fused_bank(klt_hip_ctx *c, Bank &K, const klt_hip_pyr_desc *d, const u
       HMARK_IN("l1_launched");
     }
   }
+  K.holds(il, lo, hi);
   return 0;
 }
 
