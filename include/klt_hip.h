@@ -222,6 +222,13 @@ int klt_hip_set_track_merge(klt_hip_ctx *ctx, int on);
    reads the image plane directly where k_min_eigen7_img applies).  Results do
    not depend on it.  klt_hip_ctx_reset restores 1. */
 int klt_hip_set_lazy_grad(klt_hip_ctx *ctx, int on);
+/* tuning hook: 1 (default) builds the image-only level 0 of klt_hip_set_lazy_grad
+   (whole gray frames whose width is a multiple of 8, with aligned rows) with
+   k_pyr_l0s, barrier-free one-wave strips; 0 with the 64x32 tiles that every
+   other level-0 build runs.  The environment variable KLT_L0_STRIP=0|1, read
+   once, overrides it for every context (A/B in one tree).  Results do not
+   depend on it.  klt_hip_ctx_reset restores 1. */
+int klt_hip_set_l0_strip(klt_hip_ctx *ctx, int on);
 /* Forward-backward (FB) consistency check, off by default.  With it on, every
    tracked frame img1 -> img2 of klt_hip_track (host or device arrays),
    klt_hip_track_sequence, klt_hip_track_frames and klt_hip_track_frames_host

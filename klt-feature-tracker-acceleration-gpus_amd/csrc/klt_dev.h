@@ -288,7 +288,9 @@ constexpr int kAffChunk = KLT_AFF_CH;
 hipError_t launch_pyr_l0(hipStream_t st, const uint8_t *src, int pitch, long stride, int W, int H, const DefTaps &T,
                          int vec_u8, int vec_out, float *img, float *gx, float *gy, float *hs, int W1, int do_hs,
                          long fs0, long fsh, int F, int ty0, int ty1, int py0 = 0, int py1 = 1 << 30, int il = 0,
-                         int fmt = KLT_HIP_FRAME_GRAY8);
+                         int fmt = KLT_HIP_FRAME_GRAY8, int strips = 0);
+// strips: the image-only level 0 of whole gray frames as k_pyr_l0s (one-wave
+// strips) where the tile kernel's interior path qualifies (klt_hip_set_l0_strip)
 // fmt: the source pixels' format (KLT_HIP_FRAME_*); pitch and stride are bytes.
 // A colour format runs the k_pyr_l0_px instances, whose phase A stages the
 // gray bytes of gray_of(); everything after phase A is k_pyr_l0's

@@ -5,6 +5,8 @@
 //                          convolve.c:37-53,273-314; pyramid.c:87-131)
 //   k_pyr_l0_px           k_pyr_l0 from RGB/BGR(A) pixels: phase A converts
 //                         as it stages (klt_hip_set_frame_format)
+//   k_pyr_l0s             the image-only level 0 of whole gray frames in
+//                         barrier-free one-wave strips (klt_hip_set_l0_strip)
 //   k_u8_to_f32 / k_rows / k_cols / k_subsample   the generic path (any sigma,
 //                         levels, subsampling), one 1-D pass per launch;
 //   k_px_to_f32           its first pass from colour pixels
@@ -760,6 +762,178 @@ __global__ __launch_bounds__(L0G<TH_>::NT) void k_pyr_l0_px(const uint8_t *__res
 }
 
 // ---------------------------------------------------------------------------
+// k_pyr_l0s: the image-only level 0 (img0 and hs, as k_pyr_l0<false, 32, true>)
+// in barrier-free one-wave strips.  A workgroup is one wave64; it owns the 192
+// columns [S, S+192), S = 192 * strip, and walks down the rows [y0, y1) of one
+// segment of one frame (blockIdx.z).  Nothing passes between workgroups: a
+// segment computes the two row-pass rows above and below it again.
+//
+// Lane l holds the four pixels px .. px+3, px = S - 32 + 4l.  Lanes 8..55 are
+// the strip's 192 pixels and the only ones that store; the 8 lanes on each
+// side are halo (3 would do; 8 keep the strip's hs columns on whole 16-column
+// slabs).  Per input row r = y0-2 .. y1+1:
+//   * the lane's u8 dword comes from a register ring loaded PF rows ahead
+//     (addresses clamped into the frame, so every load is unconditional);
+//   * the sigma-0.7 rows pass of its 4 pixels takes pixels px-2 .. px+5: the
+//     upper two bytes of lane l-1's dword and the lower two of lane l+1's (DPP);
+//   * the last five rows-pass results are the column window: the columns pass
+//     gives img0 row y = r-2, stored as one 16-byte piece per lane (768
+//     contiguous bytes per wave);
+//   * the img0 row also goes to a wave-private LDS row (two, used in turn:
+//     one wave-scope fence per row), from which the lane reads the 21 values
+//     px-8 .. px+12 around its column c = px+2 = 4X+2 for the sigma-3.6 rows
+//     pass; hs[y][X] is stored 4 bytes per lane, three 64-byte slab pieces.
+// Every sum has the tile kernel's order and start, so the bits are the same.
+//
+// What a lane lacks only feeds halo lanes:
+//   * rows pass of lane l reads the dwords of lanes l-1, l, l+1.  Lane 0 has
+//     no left and lane 63 no right neighbour (DPP leaves the own dword), so
+//     t1 and img0 are exact on lanes 1..62 wherever their pixels are in the
+//     frame (in-frame dwords are never clamped: W % 4 == 0);
+//   * hs of lane l reads img0 of pixels 4l-8 .. 4l+12 relative to lane 0,
+//     i.e. of lanes l-2 .. l+3: exact for l = 3..59, and lanes 0..2 and
+//     61..63 read the LDS row's pads.  Stores come from lanes 8..55 alone.
+//   * a lane outside the frame (px < 0 or px >= W, edge strips) holds clamped
+//     bytes.  A stored hs value reads them only if c-10 < 0 or c+10 >= W,
+//     which is where the zero-border rule (RP <= c < W-RP) makes it 0; a
+//     stored img0 pixel x reads x-2 .. x+2 outside the frame only where
+//     RS <= x < W-RS fails, and its t1 is then 0 by that rule.
+// EDGE: the zero-border rules are applied per element; otherwise no stored
+// value is touched by one (S >= 192, S + 206 <= W, 2 <= y0, y1 <= H-2).
+// ---------------------------------------------------------------------------
+namespace l0s {
+constexpr int SW = 192;            // columns a strip stores
+constexpr int HALO = 32;           // pixels of halo lanes on each side
+constexpr int PITCH = 8 + 256 + 16;  // floats of one LDS row: 8 of pad, the wave's 256, 16 of pad
+constexpr int kSeg = 108;          // rows per segment (launch_pyr_l0s)
+constexpr int kRing = 10;          // rows the u8 ring runs ahead
+constexpr int lcm(int a, int b) {
+  int x = a;
+  while (x % b) x += a;
+  return x;
+}
+}  // namespace l0s
+
+// lane l-1's / lane l+1's value (lane 0 / lane 63 keep their own)
+__device__ __forceinline__ uint32_t lane_left(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t lane_right(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
+}
+// a wave's LDS operations are performed in order: the fences only keep the
+// compiler from moving accesses across (as wave_lds_sync in track7.hip)
+__device__ __forceinline__ void l0s_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int PF, bool EDGE>
+__device__ __forceinline__ void pyr_l0_strip(float *__restrict__ lds, const uint8_t *__restrict__ src, int spitch, int W,
+                                             int H, const DefTaps &T, float *__restrict__ img0,
+                                             float *__restrict__ hs, int S, int y0, int y1) {
+  constexpr int RS = kRS, RP = kRP, U = l0s::lcm(10, PF), PITCH = l0s::PITCH;
+  const int lane = threadIdx.x;
+  const int px = S - l0s::HALO + 4 * lane;
+  const uint8_t *col = src + clampi(px, 0, W - 4);
+  const bool stores = lane >= 8 && lane < 56 && px < W;  // W % 4 == 0: the whole group is inside
+  const int X = px >> 2;
+  bool okx[4], okc = true;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) okx[e] = px + e >= RS && px + e < W - RS;
+  okc = px + 2 >= RP && px + 2 < W - RP;
+  float *wr = lds + 8 + 4 * lane;
+
+  uint32_t ring[PF];
+#pragma unroll
+  for (int k = 0; k < PF; ++k)
+    ring[k] = *reinterpret_cast<const uint32_t *>(col + (unsigned)(clampi(y0 - RS + k, 0, H - 1) * spitch));
+  f4 win[5];
+  int r = y0 - RS;  // the input row of the step
+  // rows pass of row r into win[WK]; the ring slot RK is loaded again PF rows ahead
+  auto rows = [&](int RK, int WK) {
+    const uint32_t d = ring[RK];
+    ring[RK] = *reinterpret_cast<const uint32_t *>(col + (unsigned)(clampi(r + PF, 0, H - 1) * spitch));
+    const uint32_t dl = lane_left(d), dr = lane_right(d);
+    const float v[8] = {(float)((dl >> 16) & 0xFF), (float)(dl >> 24),          (float)(d & 0xFF),  (float)((d >> 8) & 0xFF),
+                        (float)((d >> 16) & 0xFF),  (float)(d >> 24),           (float)(dr & 0xFF), (float)((dr >> 8) & 0xFF)};
+    f4 a = mul4(v, T.s[0]);
+#pragma unroll
+    for (int m = 1; m < 5; ++m) mac4(a, v + m, T.s[m]);
+    if (EDGE) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (!okx[e]) a[e] = 0.0f;
+    }
+    win[WK] = a;
+  };
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {  // the first four rows fill the window
+    rows(k % PF, k);
+    ++r;
+  }
+  const int rend = y1 + RS;
+  while (r < rend) {
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+      if (r >= rend) continue;  // wave-uniform; the steps left of the last round
+      rows((k + 4) % PF, (k + 4) % 5);
+      // columns pass: img0 row y = r-2 from the rows-pass rows r-4 .. r
+      const int y = r - RS;
+      f4 acc = mul4(reinterpret_cast<const float *>(&win[(k + 0) % 5]), T.s[0]);
+#pragma unroll
+      for (int m = 1; m < 5; ++m) mac4(acc, reinterpret_cast<const float *>(&win[(k + m) % 5]), T.s[m]);
+      if (EDGE && !(y >= RS && y < H - RS)) acc = f4{0.0f, 0.0f, 0.0f, 0.0f};
+      if (stores) st4_out(img0 + (unsigned)(y * W + px), acc);
+      float *b = wr + (k & 1) * PITCH;
+      st4(b, acc);
+      l0s_lds_sync();
+      // sigma-3.6 rows pass at c = px+2: img0 of pixels px-8 .. px+12
+      const f4 q0 = ld4(b - 8), q1 = ld4(b - 4), q3 = ld4(b + 4), q4 = ld4(b + 8);
+      const float q5 = b[12];
+      const float w[21] = {q0.x,  q0.y,  q0.z,  q0.w, q1.x, q1.y, q1.z, q1.w, acc.x, acc.y, acc.z,
+                           acc.w, q3.x,  q3.y,  q3.z, q3.w, q4.x, q4.y, q4.z, q4.w,  q5};
+      // one output per lane: a serial chain of scalar operations.  Left to
+      // itself the compiler packs the products in pairs, which costs a move
+      // and a wait state per pair; the empty asm keeps each one apart
+      float h = w[0] * T.p[0];  // terms >= +0
+#pragma unroll
+      for (int m = 1; m < 21; ++m) {
+        float t = w[m] * T.p[m];
+        asm("" : "+v"(t));
+        h += t;
+      }
+      if (EDGE && !okc) h = 0.0f;
+      if (stores) hs[hs_at32(y, X, H)] = h;
+      ++r;
+    }
+  }
+}
+
+// grid.x = xcd_grid(nstrips * nseg) in the XCD-aware order of xcd_tile over
+// (strip, segment), so that one XCD's L2 sees one band of rows
+// 64 VGPRs, no scratch, 8 waves per SIMD (tests/test_l0_strip_resources.py).
+// No waves-per-SIMD argument in the launch bounds: with (64, 8) the compiler
+// also holds the kernel to 78 scalar registers and spills 15 of them, the
+// sigma-3.6 taps among them, which every row then reads back lane by lane.
+template <int PF>
+__global__ __launch_bounds__(64) void k_pyr_l0s(const uint8_t *__restrict__ src, int spitch, int W, int H, DefTaps T,
+                                                   float *__restrict__ img0, float *__restrict__ hs, long fs_src,
+                                                   long fs0, long fs_hs, int nstrips, int nseg, int seg) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * l0s::PITCH];
+  int sx, sg;
+  if (!xcd_tile(nstrips, nseg, sx, sg)) return;
+  const int S = sx * l0s::SW, y0 = sg * seg, y1 = min(y0 + seg, H);
+  src += blockIdx.z * fs_src;
+  img0 += blockIdx.z * fs0;
+  hs += blockIdx.z * fs_hs;
+  const bool inside = S >= l0s::SW && S + 206 <= W && y0 >= kRS && y1 <= H - kRS;
+  if (inside) pyr_l0_strip<PF, false>(lds, src, spitch, W, H, T, img0, hs, S, y0, y1);
+  else pyr_l0_strip<PF, true>(lds, src, spitch, W, H, T, img0, hs, S, y0, y1);
+}
+
+// ---------------------------------------------------------------------------
 // k_pyr_l1: img1 = cols_p(hs) sampled at rows 4Y+2 (rest of pyramid.c:114-124)
 // and its gradients.  One 256-thread workgroup per 32 x TH tile of level 1:
 // TH = 32 for batches (geom::L1_TH: the band bookkeeping's unit), TH = 8 for
@@ -1411,6 +1585,15 @@ bool l0_wide() {
   return on;
 }
 
+// KLT_L0_STRIP=0 / 1 overrides klt_hip_set_l0_strip for every context (A/B in one tree)
+bool l0_strips(int ctx_choice) {
+  static const int env = [] {
+    const char *v = getenv("KLT_L0_STRIP");
+    return (v && *v) ? (atoi(v) != 0 ? 1 : 0) : -1;
+  }();
+  return env >= 0 ? env != 0 : ctx_choice != 0;
+}
+
 namespace {
 // launch_pyr_l0 for a colour format: the same choice of tiles and instance
 template <int FMT>
@@ -1451,7 +1634,7 @@ hipError_t launch_pyr_l0_px(hipStream_t st, const uint8_t *src, int pitch, long 
 
 hipError_t launch_pyr_l0(hipStream_t st, const uint8_t *src, int pitch, long stride, int W, int H, const DefTaps &T,
                          int vec_u8, int vec_out, float *img, float *gx, float *gy, float *hs, int W1, int do_hs,
-                         long fs0, long fsh, int F, int ty0, int ty1, int py0, int py1, int il, int fmt) {
+                         long fs0, long fsh, int F, int ty0, int ty1, int py0, int py1, int il, int fmt, int strips) {
   const int tx = (W + l0::TW - 1) / l0::TW;
   if (F <= 0 || ty1 <= ty0) return hipSuccess;
   switch (fmt) {
@@ -1476,6 +1659,15 @@ hipError_t launch_pyr_l0(hipStream_t st, const uint8_t *src, int pitch, long str
   // against 29.8-29.9 us per frame; 1080p 7.54-7.60 against 7.25 (more edge
   // tiles, and ~one workgroup per slot: the launch's tail)
   const int nty = (H + l0::G32::TH - 1) / l0::G32::TH;
+  // the image-only level 0 of a whole frame in one-wave strips, for the shapes
+  // whose tiles would take the interior path (k_pyr_l0's `interior`)
+  if (l0_strips(strips) && il == kLayoutImg && do_hs && ty0 == 0 && ty1 == nty && py0 == 0 && py1 >= nty && vec_u8 &&
+      vec_out && W1 * l0::SS == W && W1 % 2 == 0) {
+    const int ns = (W + l0s::SW - 1) / l0s::SW, nseg = (H + l0s::kSeg - 1) / l0s::kSeg;
+    hipLaunchKernelGGL(k_pyr_l0s<l0s::kRing>, dim3(xcd_grid(ns * nseg), 1, F), dim3(kWave), 0, st, src, pitch, W, H, T,
+                       img, hs, stride, fs0, fsh, ns, nseg, l0s::kSeg);
+    return hipGetLastError();
+  }
   if (l0_wide() && H >= kL0WideMinRows && ty0 == 0 && ty1 == nty && py0 == 0 && py1 >= nty) {
     using G = L0G<64>;
     const int ty = (H + G::TH - 1) / G::TH;

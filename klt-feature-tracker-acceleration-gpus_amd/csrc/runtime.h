@@ -216,6 +216,7 @@ struct __attribute__((visibility("default"))) klt_hip_ctx {  // its constructor 
   int track_order = 0;  // 0: band-sorted, XCD-major processing order; 1: input order
   int track_patch = 1;  // one-feature waves gather through a lane patch when the window fits
   int track_merge = 1;   // defer finest-level residues into the next frame's first pass (ResCarry)
+  int l0_strip = 1;  // klt_hip_set_l0_strip: the image-only level 0 of whole frames as k_pyr_l0s
   int lazy_grad = KLT_LAZY_GRAD_DEFAULT;  // klt_hip_set_lazy_grad: image-only level 0 in the banks of plain batched calls
   RTaps lazy_gg, lazy_gd;  // the gradient taps of the last such call (a kept image-only frame is made whole with them)
   int track_prio = 1;    // tracker waves at issue priority 3 (klt_hip_set_track_prio)

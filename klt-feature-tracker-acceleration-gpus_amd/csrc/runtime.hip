@@ -315,6 +315,7 @@ KLT_API int klt_hip_ctx_reset(klt_hip_ctx *c) {
   c->track_patch = 1;
   c->track_merge = 1;
   c->lazy_grad = KLT_LAZY_GRAD_DEFAULT;
+  c->l0_strip = 1;
   c->track_prio = 1;
   c->track_impl = 0;
   c->track_kernel = nullptr;  // klt_hip_track_kernel: "" before the next owner's first launch
@@ -620,6 +621,12 @@ KLT_API int klt_hip_set_track_patch(klt_hip_ctx *c, int on) {
 KLT_API int klt_hip_set_lazy_grad(klt_hip_ctx *c, int on) {
   if (!c) return fail(c, "set_lazy_grad: null context");
   c->lazy_grad = on ? 1 : 0;
+  return 0;
+}
+
+KLT_API int klt_hip_set_l0_strip(klt_hip_ctx *c, int on) {
+  if (!c) return fail(c, "set_l0_strip: null context");
+  c->l0_strip = on ? 1 : 0;
   return 0;
 }
 

@@ -117,7 +117,8 @@ int launch_l0(klt_hip_ctx *c, hipStream_t st, const uint8_t *src, long pitch, lo
     *p1 = py1 >= nty ? H : py1 * TH;
   }
   return launched(c, "k_pyr_l0", launch_pyr_l0(st, src, (int)pitch, stride, W, H, T, vec_u8, vec_out, img, gx, gy,
-                                               hs, W1, do_hs, fs0, fsh, F, ty0, ty1, py0, py1, il, fmt));
+                                               hs, W1, do_hs, fs0, fsh, F, ty0, ty1, py0, py1, il, fmt,
+                                               c->l0_strip));
 }
 
 // KLT_L1_THIN=0: a single frame's level 1 in 32-row tiles too (A/B)

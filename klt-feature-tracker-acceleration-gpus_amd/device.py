@@ -106,6 +106,7 @@ DEVICE_PROTOS = {
     "klt_hip_set_track_order": (C.c_int, [V, C.c_int]),
     "klt_hip_set_track_merge": (C.c_int, [V, C.c_int]),
     "klt_hip_set_lazy_grad": (C.c_int, [V, C.c_int]),
+    "klt_hip_set_l0_strip": (C.c_int, [V, C.c_int]),
     "klt_hip_set_track_prio": (C.c_int, [V, C.c_int]),
     "klt_hip_set_track_impl": (C.c_int, [V, C.c_int]),
     "klt_hip_set_track_patch": (C.c_int, [V, C.c_int]),
