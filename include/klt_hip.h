@@ -198,7 +198,7 @@ int klt_hip_set_path(klt_hip_ctx *ctx, int force_generic);
    covers at most 32 tracked frames), so the next call sorts afresh. */
 int klt_hip_set_track_order(klt_hip_ctx *ctx, int input_order);
 /* tracker kernel for the default configuration (7x7 window, exact sums, no
-   gain/bias): 0 (default) the latency-lean k_track7 (track7.hip), 1 the
+   gain/bias): 0 (default) the latency-lean k_track7 (track7_kernels.h), 1 the
    generic k_track_frames_g; identical results (A/B hook) */
 int klt_hip_set_track_impl(klt_hip_ctx *ctx, int impl);
 /* tuning hook: 1 (default) folds the finest level's residue pass of frame j

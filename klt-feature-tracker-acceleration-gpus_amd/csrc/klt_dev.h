@@ -9,7 +9,10 @@
 //   track7.hip    k_track7 (the Newton loop of the default configuration)
 //                 both with forward-backward instances (k_*_fb), k_track7 with
 //                 multi-sequence ones (k_track7_multi); the kernels' bodies
-//                 are track_body.h / track7_body.h
+//                 are track_body.h / track7_body.h.  k_track7's templates and
+//                 device code are track7_kernels.h, which track7_pred.hip and
+//                 track7_mask.hip include as well for the motion-prior and
+//                 region-mask instances, code objects of their own
 //   affine.hip    k_affine (the affine consistency check, one frame pair per
 //                 launch); its per-feature stage is affine_dev.h, which
 //                 track.hip's k_track_frames_g_aff runs inside the batched launch
@@ -281,6 +284,16 @@ constexpr int kAffChunk = KLT_AFF_CH;
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
+// A launcher's choice among a kernel's instances yields one row of a table: the
+// name klt_hip_track_kernel / klt_hip_eigen_kernel report (the instance as
+// rocprofv3 names it; bench.py matches counter summaries on it) beside the
+// kernel that is launched.  K: the pointer type of the kernels' argument list.
+template <class K>
+struct KernelRow {
+  const char *name;
+  K kernel;
+};
+
 // k_pyr_l0 over F frames (src + f*stride; outputs + f*fs0, hs + f*fsh), level-0
 // tile rows [ty0, ty1) of 32-row tiles; only tile rows [py0, py1) store the
 // level-0 planes (the others only the sigma-3.6 rows pass, hs)
@@ -361,10 +374,11 @@ size_t track_affine_lds_bytes(int mode);
 hipError_t launch_track7(hipStream_t st, bool band, const TrkArgs &a, const TrkFramesArgs &b, float *x, float *y,
                          int *v, int n, const char **name = nullptr, const TrkFbArgs *fb = nullptr,
                          const TrkPredArgs *pr = nullptr, const TrkMaskArgs *mk = nullptr);
-// track7_pred.hip: the k_track7_pred instances, for launch_track7 (a with the bounds thresholds, its grid and depth)
+// track7_pred.hip (track7_kernels.h's k_track7_pred instances), for launch_track7: a with the bounds thresholds, its
+// grid and depth
 hipError_t launch_track7_pred(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkPredArgs &pr, float *x,
                               float *y, int *v, int n, int grid, bool two, const char **name);
-// track7_mask.hip: the k_track7_mask instances, in the same way
+// track7_mask.hip (the k_track7_mask and k_track7_mask_lazy instances), in the same way
 hipError_t launch_track7_mask(hipStream_t st, const TrkArgs &a, const TrkFramesArgs &b, const TrkMaskArgs &mk, float *x,
                               float *y, int *v, int n, int grid, bool two, const char **name);
 // the multi-sequence instances (whole-frame interleaved pyramids, exact sums)

@@ -822,7 +822,7 @@ __device__ __forceinline__ uint32_t lane_right(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
 }
 // a wave's LDS operations are performed in order: the fences only keep the
-// compiler from moving accesses across (as wave_lds_sync in track7.hip)
+// compiler from moving accesses across (as wave_lds_sync in track7_kernels.h)
 __device__ __forceinline__ void l0s_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -1595,40 +1595,39 @@ bool l0_strips(int ctx_choice) {
 }
 
 namespace {
-// launch_pyr_l0 for a colour format: the same choice of tiles and instance
+// k_pyr_l0 and k_pyr_l0_px take one argument list
+using L0Kernel = decltype(&k_pyr_l0<false, 32>);
+
+// [64-row tiles][level-0 layout: kLayoutPlanes, kLayoutRec, kLayoutImg]
 template <int FMT>
-hipError_t launch_pyr_l0_px(hipStream_t st, const uint8_t *src, int pitch, long stride, int W, int H, const DefTaps &T,
-                            int vec_u8, int vec_out, float *img, float *gx, float *gy, float *hs, int W1, int do_hs,
-                            long fs0, long fsh, int F, int ty0, int ty1, int py0, int py1, int il) {
-  const int tx = (W + l0::TW - 1) / l0::TW;
-  const int nty = (H + l0::G32::TH - 1) / l0::G32::TH;
-  if (l0_wide() && H >= kL0WideMinRows && ty0 == 0 && ty1 == nty && py0 == 0 && py1 >= nty) {
-    using G = L0G<64>;
-    const int ty = (H + G::TH - 1) / G::TH;
-    const dim3 grid(xcd_grid(tx * ty), 1, F);
-    if (il == kLayoutImg)
-      hipLaunchKernelGGL((k_pyr_l0_px<false, 64, true, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8, img,
-                         gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
-    else if (il)
-      hipLaunchKernelGGL((k_pyr_l0_px<true, 64, false, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8, img,
-                         gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
-    else
-      hipLaunchKernelGGL((k_pyr_l0_px<false, 64, false, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8,
-                         img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
-    return hipGetLastError();
+L0Kernel l0_kernel_of(bool wide, int il) {
+  if constexpr (FMT == KLT_HIP_FRAME_GRAY8) {
+    static const L0Kernel k[2][3] = {
+        {k_pyr_l0<false, 32>, k_pyr_l0<true, 32>, k_pyr_l0<false, 32, true>},
+        {k_pyr_l0<false, 64>, k_pyr_l0<true, 64>, k_pyr_l0<false, 64, true>},
+    };
+    return k[wide][il];
+  } else {
+    static const L0Kernel k[2][3] = {
+        {k_pyr_l0_px<false, 32, false, FMT>, k_pyr_l0_px<true, 32, false, FMT>, k_pyr_l0_px<false, 32, true, FMT>},
+        {k_pyr_l0_px<false, 64, false, FMT>, k_pyr_l0_px<true, 64, false, FMT>, k_pyr_l0_px<false, 64, true, FMT>},
+    };
+    return k[wide][il];
   }
-  using G = l0::G32;
-  const dim3 grid(xcd_grid(tx * (ty1 - ty0)), 1, F);
-  if (il == kLayoutImg)
-    hipLaunchKernelGGL((k_pyr_l0_px<false, 32, true, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8, img,
-                       gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0, py0, py1);
-  else if (il)
-    hipLaunchKernelGGL((k_pyr_l0_px<true, 32, false, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8, img,
-                       gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0, py0, py1);
-  else
-    hipLaunchKernelGGL((k_pyr_l0_px<false, 32, false, FMT>), grid, dim3(G::NT), 0, st, src, pitch, W, H, T, vec_u8, img,
-                       gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0, py0, py1);
-  return hipGetLastError();
+}
+
+// the level-0 tile kernel of a source format; a format without instances has none
+L0Kernel l0_kernel(int fmt, bool wide, int il) {
+  static_assert(kLayoutPlanes == 0 && kLayoutRec == 1 && kLayoutImg == 2, "l0_kernel_of's tables");
+  il = il == kLayoutImg ? kLayoutImg : il ? kLayoutRec : kLayoutPlanes;
+  switch (fmt) {
+    case KLT_HIP_FRAME_GRAY8: return l0_kernel_of<KLT_HIP_FRAME_GRAY8>(wide, il);
+    case KLT_HIP_FRAME_RGB8: return l0_kernel_of<KLT_HIP_FRAME_RGB8>(wide, il);
+    case KLT_HIP_FRAME_BGR8: return l0_kernel_of<KLT_HIP_FRAME_BGR8>(wide, il);
+    case KLT_HIP_FRAME_RGBA8: return l0_kernel_of<KLT_HIP_FRAME_RGBA8>(wide, il);
+    case KLT_HIP_FRAME_BGRA8: return l0_kernel_of<KLT_HIP_FRAME_BGRA8>(wide, il);
+    default: return nullptr;
+  }
 }
 }  // namespace
 
@@ -1637,63 +1636,34 @@ hipError_t launch_pyr_l0(hipStream_t st, const uint8_t *src, int pitch, long str
                          long fs0, long fsh, int F, int ty0, int ty1, int py0, int py1, int il, int fmt, int strips) {
   const int tx = (W + l0::TW - 1) / l0::TW;
   if (F <= 0 || ty1 <= ty0) return hipSuccess;
-  switch (fmt) {
-    case KLT_HIP_FRAME_GRAY8: break;
-#define KLT_L0_PX(f)                                                                                               \
-  case f:                                                                                                          \
-    return launch_pyr_l0_px<f>(st, src, pitch, stride, W, H, T, vec_u8, vec_out, img, gx, gy, hs, W1, do_hs, fs0, \
-                               fsh, F, ty0, ty1, py0, py1, il);
-      KLT_L0_PX(KLT_HIP_FRAME_RGB8)
-      KLT_L0_PX(KLT_HIP_FRAME_BGR8)
-      KLT_L0_PX(KLT_HIP_FRAME_RGBA8)
-      KLT_L0_PX(KLT_HIP_FRAME_BGRA8)
-#undef KLT_L0_PX
-    default: return hipErrorInvalidValue;  // a missing instance is an error, never the gray kernel
-  }
-#ifdef KLT_EXP_NOHS  // timing experiment only: level 0 without the sigma-3.6 rows pass
-  do_hs = 0;
-#endif
-  // a whole 4K-class frame with every tile's planes (ty, py in 32-row tiles)
-  // runs the 64-row tiles; a band, planes for some rows only, or a shorter
-  // frame the 32-row ones.  Same-box A/B (tools/exp/r04x.sh): 4K 29.4
-  // against 29.8-29.9 us per frame; 1080p 7.54-7.60 against 7.25 (more edge
-  // tiles, and ~one workgroup per slot: the launch's tail)
+  // a whole frame with every tile's planes (ty, py in 32-row tiles)
   const int nty = (H + l0::G32::TH - 1) / l0::G32::TH;
-  // the image-only level 0 of a whole frame in one-wave strips, for the shapes
-  // whose tiles would take the interior path (k_pyr_l0's `interior`)
-  if (l0_strips(strips) && il == kLayoutImg && do_hs && ty0 == 0 && ty1 == nty && py0 == 0 && py1 >= nty && vec_u8 &&
-      vec_out && W1 * l0::SS == W && W1 % 2 == 0) {
+  const bool whole = ty0 == 0 && ty1 == nty && py0 == 0 && py1 >= nty;
+  // the image-only level 0 of a whole gray frame in one-wave strips, for the
+  // shapes whose tiles would take the interior path (k_pyr_l0's `interior`)
+  if (fmt == KLT_HIP_FRAME_GRAY8 && l0_strips(strips) && il == kLayoutImg && do_hs && whole && vec_u8 && vec_out &&
+      W1 * l0::SS == W && W1 % 2 == 0) {
     const int ns = (W + l0s::SW - 1) / l0s::SW, nseg = (H + l0s::kSeg - 1) / l0s::kSeg;
     hipLaunchKernelGGL(k_pyr_l0s<l0s::kRing>, dim3(xcd_grid(ns * nseg), 1, F), dim3(kWave), 0, st, src, pitch, W, H, T,
                        img, hs, stride, fs0, fsh, ns, nseg, l0s::kSeg);
     return hipGetLastError();
   }
-  if (l0_wide() && H >= kL0WideMinRows && ty0 == 0 && ty1 == nty && py0 == 0 && py1 >= nty) {
+  // a whole 4K-class frame runs the 64-row tiles; a band, planes for some rows
+  // only, or a shorter frame the 32-row ones.  Same-box A/B (tools/exp/r04x.sh):
+  // 4K 29.4 against 29.8-29.9 us per frame; 1080p 7.54-7.60 against 7.25 (more
+  // edge tiles, and ~one workgroup per slot: the launch's tail)
+  const bool wide = l0_wide() && H >= kL0WideMinRows && whole;
+  const L0Kernel k = l0_kernel(fmt, wide, il);
+  if (!k) return hipErrorInvalidValue;  // a missing instance is an error, never the gray kernel
+  int nt = l0::G32::NT;
+  if (wide) {  // all of the frame's 64-row tiles, every one with its planes
     using G = L0G<64>;
-    const int ty = (H + G::TH - 1) / G::TH;
-    if (il == kLayoutImg)
-      hipLaunchKernelGGL((k_pyr_l0<false, 64, true>), dim3(xcd_grid(tx * ty), 1, F), dim3(G::NT), 0, st, src, pitch, W,
-                         H, T, vec_u8, img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
-    else if (il)
-      hipLaunchKernelGGL((k_pyr_l0<true, 64>), dim3(xcd_grid(tx * ty), 1, F), dim3(G::NT), 0, st, src, pitch, W, H, T,
-                         vec_u8, img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
-    else
-      hipLaunchKernelGGL((k_pyr_l0<false, 64>), dim3(xcd_grid(tx * ty), 1, F), dim3(G::NT), 0, st, src, pitch, W, H,
-                         T, vec_u8, img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, 0, tx, ty, 0, ty);
-    return hipGetLastError();
+    ty0 = py0 = 0;
+    ty1 = py1 = (H + G::TH - 1) / G::TH;
+    nt = G::NT;
   }
-  using G = l0::G32;
-  if (il == kLayoutImg)
-    hipLaunchKernelGGL((k_pyr_l0<false, 32, true>), dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(G::NT), 0, st, src,
-                       pitch, W, H, T, vec_u8, img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0,
-                       py0, py1);
-  else if (il)
-    hipLaunchKernelGGL((k_pyr_l0<true, 32>), dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(G::NT), 0, st, src, pitch, W,
-                       H, T, vec_u8, img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0, py0, py1);
-  else
-    hipLaunchKernelGGL((k_pyr_l0<false, 32>), dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(G::NT), 0, st, src, pitch,
-                       W, H, T, vec_u8, img, gx, gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0, py0,
-                       py1);
+  hipLaunchKernelGGL(k, dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(nt), 0, st, src, pitch, W, H, T, vec_u8, img, gx,
+                     gy, hs, W1, do_hs, vec_out, stride, fs0, fsh, ty0, tx, ty1 - ty0, py0, py1);
   return hipGetLastError();
 }
 
@@ -1702,21 +1672,11 @@ hipError_t launch_pyr_l1(hipStream_t st, const float *hs, int W1, int H, int H1,
                          int thin) {
   const int tx = (W1 + geom::L1_TW - 1) / geom::L1_TW;
   if (F <= 0 || ty1 <= ty0) return hipSuccess;
-  if (thin) {  // single frame: ty0/ty1 in 8-row tiles
-    if (il)
-      hipLaunchKernelGGL((k_pyr_l1<true, kL1ThinTH>), dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(256), 0, st, hs,
-                         W1, H, H1, T, vec, img1, gx1, gy1, fsh, fs1, ty0, tx, ty1 - ty0);
-    else
-      hipLaunchKernelGGL((k_pyr_l1<false, kL1ThinTH>), dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(256), 0, st, hs,
-                         W1, H, H1, T, vec, img1, gx1, gy1, fsh, fs1, ty0, tx, ty1 - ty0);
-    return hipGetLastError();
-  }
-  if (il)
-    hipLaunchKernelGGL((k_pyr_l1<true, geom::L1_TH>), dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(256), 0, st, hs,
-                       W1, H, H1, T, vec, img1, gx1, gy1, fsh, fs1, ty0, tx, ty1 - ty0);
-  else
-    hipLaunchKernelGGL((k_pyr_l1<false, geom::L1_TH>), dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(256), 0, st, hs,
-                       W1, H, H1, T, vec, img1, gx1, gy1, fsh, fs1, ty0, tx, ty1 - ty0);
+  // thin: a single frame, ty0/ty1 in 8-row tiles
+  const auto k = thin ? (il ? k_pyr_l1<true, kL1ThinTH> : k_pyr_l1<false, kL1ThinTH>)
+                      : (il ? k_pyr_l1<true, geom::L1_TH> : k_pyr_l1<false, geom::L1_TH>);
+  hipLaunchKernelGGL(k, dim3(xcd_grid(tx * (ty1 - ty0)), 1, F), dim3(256), 0, st, hs, W1, H, H1, T, vec, img1, gx1,
+                     gy1, fsh, fs1, ty0, tx, ty1 - ty0);
   return hipGetLastError();
 }
 
@@ -1787,23 +1747,27 @@ hipError_t launch_subsample(hipStream_t st, const float *in, int W, int ss, floa
   return hipGetLastError();
 }
 
+// the 7x7 map kernels' grid: one workgroup per eig::TX x eig::TY tile of the map
+static unsigned eig_tiles(int nx, int ny) {
+  return (unsigned)((long)((nx + eig::TX - 1) / eig::TX) * ((ny + eig::TY - 1) / eig::TY));
+}
+
 hipError_t launch_min_eigen(hipStream_t st, const float *gx, const float *gy, int W, int ps, int bx, int by, int step,
                             int nx, int ny, int hw, int hh, int *out, const char **name) {
   const long np = (long)nx * ny;
   if (np == 0) return hipSuccess;
-  const bool win7 = hw == eig::HW && hh == eig::HW && step >= 1 && step <= eig::kMaxStep;
-  if (name)
-    *name = !win7       ? "kltdev::(anonymous namespace)::k_min_eigen"
-            : step == 1 ? "kltdev::(anonymous namespace)::k_min_eigen7<1>"
-                        : "kltdev::(anonymous namespace)::k_min_eigen7<2>";
-  if (win7) {
-    const long tiles = (long)((nx + eig::TX - 1) / eig::TX) * ((ny + eig::TY - 1) / eig::TY);
-    if (step == 1)
-      hipLaunchKernelGGL(k_min_eigen7<1>, dim3((unsigned)tiles), dim3(256), 0, st, gx, gy, W, ps, bx, by, nx, ny, out);
-    else
-      hipLaunchKernelGGL(k_min_eigen7<2>, dim3((unsigned)tiles), dim3(256), 0, st, gx, gy, W, ps, bx, by, nx, ny, out);
+  if (hw == eig::HW && hh == eig::HW && step >= 1 && step <= eig::kMaxStep) {
+    static const KernelRow<decltype(&k_min_eigen7<1>)> rows[2] = {
+        {"kltdev::(anonymous namespace)::k_min_eigen7<1>", k_min_eigen7<1>},
+        {"kltdev::(anonymous namespace)::k_min_eigen7<2>", k_min_eigen7<2>},
+    };
+    const auto &row = rows[step != 1];
+    if (name) *name = row.name;
+    hipLaunchKernelGGL(row.kernel, dim3(eig_tiles(nx, ny)), dim3(256), 0, st, gx, gy, W, ps, bx, by, nx, ny, out);
     return hipGetLastError();
   }
+  // any other window or step: the generic kernel, with an argument list of its own
+  if (name) *name = "kltdev::(anonymous namespace)::k_min_eigen";
   hipLaunchKernelGGL(k_min_eigen, dim3(blocks_for(np)), dim3(kBlock), 0, st, gx, gy, W, ps, bx, by, step, nx, ny, hw,
                      hh, out);
   return hipGetLastError();
@@ -1814,15 +1778,14 @@ hipError_t launch_min_eigen_multi(hipStream_t st, const float *rec, long frame_s
   if ((long)nx * ny == 0 || m.nsel == 0) return hipSuccess;
   if (step < 1 || step > eig::kMaxStep || m.nsel < 0 || m.nsel > kMaxSeq || bx < eig::HW || by < eig::HW)
     return hipErrorInvalidValue;
-  if (name)
-    *name = step == 1 ? "kltdev::(anonymous namespace)::k_min_eigen7_multi<1>"
-                      : "kltdev::(anonymous namespace)::k_min_eigen7_multi<2>";
-  const long tiles = (long)((nx + eig::TX - 1) / eig::TX) * ((ny + eig::TY - 1) / eig::TY);
-  const dim3 grid((unsigned)tiles, (unsigned)m.nsel);
-  if (step == 1)
-    hipLaunchKernelGGL(k_min_eigen7_multi<1>, grid, dim3(256), 0, st, rec, frame_stride, m, W, bx, by, nx, ny, maps);
-  else
-    hipLaunchKernelGGL(k_min_eigen7_multi<2>, grid, dim3(256), 0, st, rec, frame_stride, m, W, bx, by, nx, ny, maps);
+  static const KernelRow<decltype(&k_min_eigen7_multi<1>)> rows[2] = {
+      {"kltdev::(anonymous namespace)::k_min_eigen7_multi<1>", k_min_eigen7_multi<1>},
+      {"kltdev::(anonymous namespace)::k_min_eigen7_multi<2>", k_min_eigen7_multi<2>},
+  };
+  const auto &row = rows[step != 1];
+  if (name) *name = row.name;
+  hipLaunchKernelGGL(row.kernel, dim3(eig_tiles(nx, ny), (unsigned)m.nsel), dim3(256), 0, st, rec, frame_stride, m, W,
+                     bx, by, nx, ny, maps);
   return hipGetLastError();
 }
 
@@ -1830,14 +1793,13 @@ hipError_t launch_min_eigen_img(hipStream_t st, const float *img, int W, int H, 
                                 int step, int nx, int ny, int *out, const char **name) {
   if ((long)nx * ny == 0) return hipSuccess;
   if (step < 1 || step > eig::kMaxStep || W < 1 || H < 1) return hipErrorInvalidValue;
-  if (name)
-    *name = step == 1 ? "kltdev::(anonymous namespace)::k_min_eigen7_img<1>"
-                      : "kltdev::(anonymous namespace)::k_min_eigen7_img<2>";
-  const long tiles = (long)((nx + eig::TX - 1) / eig::TX) * ((ny + eig::TY - 1) / eig::TY);
-  if (step == 1)
-    hipLaunchKernelGGL(k_min_eigen7_img<1>, dim3((unsigned)tiles), dim3(256), 0, st, img, W, H, t, bx, by, nx, ny, out);
-  else
-    hipLaunchKernelGGL(k_min_eigen7_img<2>, dim3((unsigned)tiles), dim3(256), 0, st, img, W, H, t, bx, by, nx, ny, out);
+  static const KernelRow<decltype(&k_min_eigen7_img<1>)> rows[2] = {
+      {"kltdev::(anonymous namespace)::k_min_eigen7_img<1>", k_min_eigen7_img<1>},
+      {"kltdev::(anonymous namespace)::k_min_eigen7_img<2>", k_min_eigen7_img<2>},
+  };
+  const auto &row = rows[step != 1];
+  if (name) *name = row.name;
+  hipLaunchKernelGGL(row.kernel, dim3(eig_tiles(nx, ny)), dim3(256), 0, st, img, W, H, t, bx, by, nx, ny, out);
   return hipGetLastError();
 }
 

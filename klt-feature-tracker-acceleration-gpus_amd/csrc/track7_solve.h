@@ -1,6 +1,6 @@
 // track7_solve.h -- the 2x2 solve of one Newton pass (_solveEquation,
 // trackFeatures.c:281-307, after the matrix and the error vector of :227-278),
-// shared by track7.hip's pass7 and the self-check kernel in pyramid.hip
+// shared by track7_kernels.h's pass7 and the self-check kernel in pyramid.hip
 // (klt_hip_selftest_solve2).  Included inside namespace kltdev; contraction is
 // off for every file (csrc/Makefile).
 //
